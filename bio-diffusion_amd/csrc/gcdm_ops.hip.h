@@ -134,23 +134,26 @@ __global__ __launch_bounds__(256) void k_colsum_slices(const float* __restrict__
 
 // ---- element-wise nonlinearities (get_nonlinearity, components/__init__.py: relu / leakyrelu / selu / silu; + sigmoid) --------------------
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_LEAKYRELU = 4, ACT_SELU = 5 };
+// expf / expm1f, not __expf: the fast exp2-based form loses relative accuracy at large negative x (SiLU, sigmoid) and `__expf(x) - 1`
+// cancels completely near 0- (SELU); the kernels are memory-bound, the accurate forms cost nothing measurable.  ReLU keeps NaN (x < 0 is
+// false for it), as torch.relu does.
 __device__ __forceinline__ float act_f(int kind, float x) {
     switch (kind) {
-        case ACT_SILU: return x / (1.f + __expf(-x));
-        case ACT_RELU: return x > 0.f ? x : 0.f;
-        case ACT_SIGMOID: return 1.f / (1.f + __expf(-x));
+        case ACT_SILU: return x / (1.f + expf(-x));
+        case ACT_RELU: return x < 0.f ? 0.f : x;
+        case ACT_SIGMOID: return 1.f / (1.f + expf(-x));
         case ACT_LEAKYRELU: return x > 0.f ? x : 0.01f * x;
-        case ACT_SELU: return 1.0507009873554804934193349852946f * (x > 0.f ? x : 1.6732632423543772848170429916717f * (__expf(x) - 1.f));
+        case ACT_SELU: return 1.0507009873554804934193349852946f * (x > 0.f ? x : 1.6732632423543772848170429916717f * expm1f(x));
         default: return x;
     }
 }
 __device__ __forceinline__ float act_df(int kind, float x) {
     switch (kind) {
-        case ACT_SILU: { const float s = 1.f / (1.f + __expf(-x)); return s * (1.f + x * (1.f - s)); }
+        case ACT_SILU: { const float s = 1.f / (1.f + expf(-x)); return s * (1.f + x * (1.f - s)); }
         case ACT_RELU: return x > 0.f ? 1.f : 0.f;
-        case ACT_SIGMOID: { const float s = 1.f / (1.f + __expf(-x)); return s * (1.f - s); }
+        case ACT_SIGMOID: { const float s = 1.f / (1.f + expf(-x)); return s * (1.f - s); }
         case ACT_LEAKYRELU: return x > 0.f ? 1.f : 0.01f;
-        case ACT_SELU: return 1.0507009873554804934193349852946f * (x > 0.f ? 1.f : 1.6732632423543772848170429916717f * __expf(x));
+        case ACT_SELU: return 1.0507009873554804934193349852946f * (x > 0.f ? 1.f : 1.6732632423543772848170429916717f * expf(x));
         default: return 1.f;
     }
 }
@@ -386,132 +389,183 @@ __global__ void k_fc_edges(const int32_t* __restrict__ noff, const int64_t* __re
 // ------------------------------------------------------------------------------------------------------------------------------------------
 #define GOPS_LAUNCH_OK() (hipGetLastError() == hipSuccess ? 0 : -2)
 static inline unsigned gops_blocks(int64_t n, int t = 256) { return (unsigned)((n + t - 1) / t); }
+// argument checks, all before any HIP call: a negative size, a flag outside its range or a null pointer the (non-empty) work needs is -1;
+// empty work is 0 without a launch
+#define GOPS_REQUIRE(cond) do { if (!(cond)) return -1; } while (0)
+static inline bool gops_flag(int32_t v) { return v == 0 || v == 1; }
 
 extern "C" {
 
 int gcdm_op_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, float* C, const float* bias, int64_t M, int32_t N,
                  int64_t K, int32_t slices, void* stream) {
-    if (!A || !B || !C || M < 0 || N < 0 || K < 0 || slices < 1) return -1;
+    GOPS_REQUIRE(M >= 0 && N >= 0 && K >= 0 && slices >= 1);
     if (M == 0 || N == 0) return 0;
+    GOPS_REQUIRE(A && B && C);
     const int64_t kslice = ((K + slices - 1) / slices + gops::GK - 1) / gops::GK * gops::GK;
     const dim3 grid((unsigned)((M + gops::GM - 1) / gops::GM), (unsigned)((N + gops::GN - 1) / gops::GN), (unsigned)slices);
     hipLaunchKernelGGL(gops::k_gemm, grid, dim3(256), 0, (hipStream_t)stream, A, sam, sak, B, sbk, sbn, C, bias, M, N, K, kslice > 0 ? kslice : gops::GK);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_reduce_slices(const float* part, float* out, int64_t n, int32_t slices, void* stream) {
-    if (n <= 0) return 0;
+    GOPS_REQUIRE(n >= 0 && slices >= 1);
+    if (n == 0) return 0;
+    GOPS_REQUIRE(part && out);
     hipLaunchKernelGGL(gops::k_reduce_slices, dim3(gops_blocks(n)), dim3(256), 0, (hipStream_t)stream, part, out, n, slices);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_colsum(const float* dy, float* db, int64_t M, int32_t N, void* stream) {
-    if (N <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && N >= 0);
+    if (N == 0) return 0;
+    GOPS_REQUIRE(db && (M == 0 || dy));
     hipLaunchKernelGGL(gops::k_colsum, dim3((N + 63) / 64), dim3(256), 0, (hipStream_t)stream, dy, db, M, N);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_colsum_slices(const float* dy, float* part, int64_t M, int32_t N, int32_t slices, void* stream) {
-    if (N <= 0 || slices <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && N >= 0 && slices >= 1);
+    if (N == 0) return 0;
+    GOPS_REQUIRE(part && (M == 0 || dy));
     const int64_t rows = (M + slices - 1) / slices;
     hipLaunchKernelGGL(gops::k_colsum_slices, dim3((N + 63) / 64, slices), dim3(256), 0, (hipStream_t)stream, dy, part, M, N, rows);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_act(int32_t kind, const float* x, float* y, int64_t n, void* stream) {
-    if (n <= 0) return 0;
+    GOPS_REQUIRE(kind >= 0 && kind <= 5 && n >= 0);
+    if (n == 0) return 0;
+    GOPS_REQUIRE(x && y);
     hipLaunchKernelGGL(gops::k_act, dim3(gops_blocks(n)), dim3(256), 0, (hipStream_t)stream, kind, x, y, n);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_act_bwd(int32_t kind, const float* x, const float* dy, float* dx, int64_t n, void* stream) {
-    if (n <= 0) return 0;
+    GOPS_REQUIRE(kind >= 0 && kind <= 5 && n >= 0);
+    if (n == 0) return 0;
+    GOPS_REQUIRE(x && dy && dx);
     hipLaunchKernelGGL(gops::k_act_bwd, dim3(gops_blocks(n)), dim3(256), 0, (hipStream_t)stream, kind, x, dy, dx, n);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_norm3(const float* v, float* out, int64_t M, int32_t C, int32_t rep_layout, void* stream) {
-    if (M * C <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && C >= 0 && gops_flag(rep_layout));
+    if (M == 0 || C == 0) return 0;
+    GOPS_REQUIRE(v && out);
     hipLaunchKernelGGL(gops::k_norm3, dim3(gops_blocks(M * C)), dim3(256), 0, (hipStream_t)stream, v, out, M * C, C, rep_layout ? 3 : 1, rep_layout ? 1 : C, 1e-8f);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_norm3_bwd(const float* v, const float* out, const float* dout, float* dv, int64_t M, int32_t C, int32_t rep_layout, void* stream) {
-    if (M * C <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && C >= 0 && gops_flag(rep_layout));
+    if (M == 0 || C == 0) return 0;
+    GOPS_REQUIRE(v && out && dout && dv);
     hipLaunchKernelGGL(gops::k_norm3_bwd, dim3(gops_blocks(M * C)), dim3(256), 0, (hipStream_t)stream, v, out, dout, dv, M * C, C, rep_layout ? 3 : 1,
                        rep_layout ? 1 : C, 1e-8f);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_scalarize(const float* u, const float* F, float* out, int64_t M, int32_t CH, void* stream) {
-    if (M * CH <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && CH >= 0);
+    if (M == 0 || CH == 0) return 0;
+    GOPS_REQUIRE(u && F && out);
     hipLaunchKernelGGL(gops::k_scalarize, dim3(gops_blocks(M * CH)), dim3(256), 0, (hipStream_t)stream, u, F, out, M, CH);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_scalarize_bwd(const float* dout, const float* F, float* du, int64_t M, int32_t CH, void* stream) {
-    if (M * CH <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && CH >= 0);
+    if (M == 0 || CH == 0) return 0;
+    GOPS_REQUIRE(dout && F && du);
     hipLaunchKernelGGL(gops::k_scalarize_bwd, dim3(gops_blocks(M * CH)), dim3(256), 0, (hipStream_t)stream, dout, F, du, M, CH);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_vectorize(const float* gate, const float* F, float* out, int64_t M, int32_t KC, void* stream) {
-    if (M * KC <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && KC >= 0);
+    if (M == 0 || KC == 0) return 0;
+    GOPS_REQUIRE(gate && F && out);
     hipLaunchKernelGGL(gops::k_vectorize, dim3(gops_blocks(M * KC)), dim3(256), 0, (hipStream_t)stream, gate, F, out, M, KC);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_vectorize_bwd(const float* dout, const float* F, float* dgate, int64_t M, int32_t KC, void* stream) {
-    if (M * KC <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && KC >= 0);
+    if (M == 0 || KC == 0) return 0;
+    GOPS_REQUIRE(dout && F && dgate);
     hipLaunchKernelGGL(gops::k_vectorize_bwd, dim3(gops_blocks(M * KC)), dim3(256), 0, (hipStream_t)stream, dout, F, dgate, M, KC);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_rowscale(const float* v, const float* g, float* out, int64_t M, int32_t C, void* stream) {
-    if (M * C <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && C >= 0);
+    if (M == 0 || C == 0) return 0;
+    GOPS_REQUIRE(v && g && out);
     hipLaunchKernelGGL(gops::k_rowscale, dim3(gops_blocks(M * C)), dim3(256), 0, (hipStream_t)stream, v, g, out, M * C);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_rowscale_bwd(const float* v, const float* g, const float* dout, float* dv, float* dg, int64_t M, int32_t C, void* stream) {
-    if (M * C <= 0) return 0;
+    GOPS_REQUIRE(M >= 0 && C >= 0);
+    if (M == 0 || C == 0) return 0;
+    GOPS_REQUIRE(v && g && dout && dv && dg);
     hipLaunchKernelGGL(gops::k_rowscale_bwd, dim3(gops_blocks(M * C)), dim3(256), 0, (hipStream_t)stream, v, g, dout, dv, dg, M * C);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_rowptr(const int64_t* row, int64_t E, int64_t N, int32_t* rowptr, int32_t* flag, void* stream) {
+    GOPS_REQUIRE(E >= 0 && N >= 0);
+    GOPS_REQUIRE(rowptr && flag && (E == 0 || row));          // never empty: rowptr has N + 1 entries
     const int64_t n = (N + 1 > E ? N + 1 : E);
     hipLaunchKernelGGL(gops::k_rowptr, dim3(gops_blocks(n)), dim3(256), 0, (hipStream_t)stream, row, E, N, rowptr, flag);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_gather(const float* x, const int64_t* idx, float* out, int64_t E, int32_t C, void* stream) {
-    if (E * C <= 0) return 0;
+    GOPS_REQUIRE(E >= 0 && C >= 0);
+    if (E == 0 || C == 0) return 0;
+    GOPS_REQUIRE(x && idx && out);
     hipLaunchKernelGGL(gops::k_gather, dim3(gops_blocks(E * C)), dim3(256), 0, (hipStream_t)stream, x, idx, out, E, C);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_segment_sum(const float* x, const int32_t* rowptr, float* out, int64_t N, int32_t C, int32_t mean, void* stream) {
-    if (N * C <= 0) return 0;
+    GOPS_REQUIRE(N >= 0 && C >= 0 && gops_flag(mean));
+    if (N == 0 || C == 0) return 0;
+    GOPS_REQUIRE(x && rowptr && out);
     hipLaunchKernelGGL(gops::k_segment_sum, dim3(gops_blocks(N * C)), dim3(256), 0, (hipStream_t)stream, x, rowptr, out, N, C, mean);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_segment_bwd(const float* dout, const int64_t* row, const int32_t* rowptr, float* dx, int64_t E, int32_t C, int32_t mean, void* stream) {
-    if (E * C <= 0) return 0;
+    GOPS_REQUIRE(E >= 0 && C >= 0 && gops_flag(mean));
+    if (E == 0 || C == 0) return 0;
+    GOPS_REQUIRE(dout && row && rowptr && dx);
     hipLaunchKernelGGL(gops::k_segment_bwd, dim3(gops_blocks(E * C)), dim3(256), 0, (hipStream_t)stream, dout, row, rowptr, dx, E, C, mean);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_scatter_add(const float* dy, const int64_t* idx, float* out, int64_t E, int32_t C, void* stream) {
-    if (E * C <= 0) return 0;
+    GOPS_REQUIRE(E >= 0 && C >= 0);
+    if (E == 0 || C == 0) return 0;
+    GOPS_REQUIRE(dy && idx && out);
     hipLaunchKernelGGL(gops::k_scatter_add, dim3(gops_blocks(E * C)), dim3(256), 0, (hipStream_t)stream, dy, idx, out, E, C);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_localize(const float* x, const int64_t* row, const int64_t* col, float* F, int64_t E, int32_t norm_x_diff, void* stream) {
-    if (E <= 0) return 0;
+    GOPS_REQUIRE(E >= 0 && gops_flag(norm_x_diff));
+    if (E == 0) return 0;
+    GOPS_REQUIRE(x && row && col && F);
     hipLaunchKernelGGL(gops::k_localize, dim3(gops_blocks(E)), dim3(256), 0, (hipStream_t)stream, x, row, col, F, E, norm_x_diff);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_edge_features(const float* x, const int64_t* row, const int64_t* col, float* e_out, float* xi_out, int64_t E, void* stream) {
-    if (E <= 0) return 0;
+    GOPS_REQUIRE(E >= 0);
+    if (E == 0) return 0;
+    GOPS_REQUIRE(x && row && col && e_out && xi_out);
     hipLaunchKernelGGL(gops::k_edge_features, dim3(gops_blocks(E)), dim3(256), 0, (hipStream_t)stream, x, row, col, e_out, xi_out, E);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_orientations(const float* x, float* out, int64_t N, void* stream) {
-    if (N <= 0) return 0;
+    GOPS_REQUIRE(N >= 0);
+    if (N == 0) return 0;
+    GOPS_REQUIRE(x && out);
     hipLaunchKernelGGL(gops::k_orientations, dim3(gops_blocks(N)), dim3(256), 0, (hipStream_t)stream, x, out, N);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_centralize(const float* x, const int64_t* batch_index, const uint8_t* mask, float* out, int64_t N, int32_t D, void* stream) {
-    if (N <= 0) return 0;
+    GOPS_REQUIRE(N >= 0 && D >= 0);
+    if (N == 0 || D == 0) return 0;
+    GOPS_REQUIRE(x && batch_index && out);                     // mask may be null: every node counts
     hipLaunchKernelGGL(gops::k_centralize, dim3(gops_blocks(N)), dim3(256), 0, (hipStream_t)stream, x, batch_index, mask, out, N, D);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_fc_edges(const int32_t* noff, const int64_t* eoff, int32_t B, int64_t* row, int64_t* col, int64_t E, void* stream) {
-    if (E <= 0) return 0;
+    GOPS_REQUIRE(B >= 0 && E >= 0);
+    if (E == 0) return 0;
+    GOPS_REQUIRE(B >= 1 && noff && eoff && row && col);
     hipLaunchKernelGGL(gops::k_fc_edges, dim3(gops_blocks(E)), dim3(256), 0, (hipStream_t)stream, noff, eoff, B, row, col, E);
     return GOPS_LAUNCH_OK();
 }

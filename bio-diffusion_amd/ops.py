@@ -32,6 +32,12 @@ def _dev(t: torch.Tensor) -> None:
         raise RuntimeError("bio-diffusion_amd operators run on an MI355X only: tensors must be on a HIP ('cuda') device; there is no CPU fallback")
 
 
+def _shape(ok: bool, what: str) -> None:
+    """Shape checks run before the device check and before any launch: a mismatched shape would make a kernel read or write out of bounds."""
+    if not ok:
+        raise ValueError(what)
+
+
 def _f(t: torch.Tensor) -> torch.Tensor:
     _dev(t)
     return t.detach().to(torch.float32).contiguous()
@@ -71,6 +77,9 @@ def _gemm(A: torch.Tensor, sam: int, sak: int, B: torch.Tensor, sbk: int, sbn: i
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
+        _shape(w.dim() == 2 and x.dim() >= 1 and x.shape[-1] == w.shape[1],
+               f"linear: input {tuple(x.shape)} does not match weight {tuple(w.shape)} (last axis must equal weight.shape[1])")
+        _shape(b is None or (b.dim() == 1 and b.shape[0] == w.shape[0]), f"linear: bias {None if b is None else tuple(b.shape)} for weight {tuple(w.shape)}")
         xs = _f(x).reshape(-1, x.shape[-1])
         ws = _f(w)
         bs = None if b is None else _f(b)
@@ -139,6 +148,8 @@ def act(x: torch.Tensor, name) -> torch.Tensor:
 class _Norm3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v, rep_layout):
+        _shape(v.dim() == 3 and v.shape[2 if rep_layout else 1] == 3,
+               f"safe_norm: vectors {tuple(v.shape)} must be [M, C, 3] (rep) / [M, 3, C] (pre)")
         vs = _f(v)
         M = vs.shape[0]
         Cn = vs.shape[1] if rep_layout else vs.shape[2]
@@ -171,6 +182,8 @@ def safe_norm_rep(v_rep: torch.Tensor) -> torch.Tensor:
 class _Scalarize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u_pre, F):
+        _shape(u_pre.dim() == 3 and u_pre.shape[1] == 3, f"scalarize: u {tuple(u_pre.shape)} must be [M, 3, CH]")
+        _shape(F.numel() == 9 * u_pre.shape[0] and F.shape[0] == u_pre.shape[0], f"scalarize: frames {tuple(F.shape)} for {u_pre.shape[0]} rows")
         us, Fs = _f(u_pre), _f(F).reshape(-1, 9)
         M, CH = us.shape[0], us.shape[2]
         out = torch.empty((M, 3 * CH), dtype=torch.float32, device=us.device)
@@ -198,6 +211,8 @@ def scalarize(u_pre: torch.Tensor, entity_frames: torch.Tensor) -> torch.Tensor:
 class _Vectorize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gate, F):
+        _shape(gate.dim() == 2 and gate.shape[1] % 3 == 0, f"vectorize: gate {tuple(gate.shape)} must be [M, 3 K]")
+        _shape(F.numel() == 9 * gate.shape[0] and F.shape[0] == gate.shape[0], f"vectorize: frames {tuple(F.shape)} for {gate.shape[0]} rows")
         gs, Fs = _f(gate), _f(F).reshape(-1, 9)
         M, KC = gs.shape[0], gs.shape[1] // 3
         out = torch.empty((M, KC, 3), dtype=torch.float32, device=gs.device)
@@ -224,6 +239,9 @@ def vectorize(gate: torch.Tensor, entity_frames: torch.Tensor) -> torch.Tensor:
 class _RowScale(torch.autograd.Function):
     @staticmethod
     def forward(ctx, v_rep, g):
+        _shape(v_rep.dim() == 3 and v_rep.shape[2] == 3, f"rowscale: vectors {tuple(v_rep.shape)} must be [M, C, 3]")
+        _shape(g.shape[0] == v_rep.shape[0] and g.numel() == v_rep.shape[0] * v_rep.shape[1],
+               f"rowscale: gate {tuple(g.shape)} for vectors {tuple(v_rep.shape)}")
         vs, gs = _f(v_rep), _f(g)
         M, Cn = vs.shape[0], vs.shape[1]
         out = torch.empty_like(vs)
@@ -242,6 +260,7 @@ class _RowScale(torch.autograd.Function):
 
 def rowscale(v_rep: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     """v_rep [M, C, 3] * g [M, C] (or [M, C, 1])."""
+    _shape(g.dim() >= 1, "rowscale: the gate must have a row axis")
     return _RowScale.apply(v_rep, g.reshape(g.shape[0], -1))
 
 
@@ -250,14 +269,26 @@ class Graph:
     """CSR view of a row-sorted edge list (what get_fully_connected_edge_index produces): rowptr on the device, built once per edge_index."""
 
     def __init__(self, edge_index: torch.Tensor, num_nodes: int):
+        _shape(edge_index.dim() == 2 and edge_index.shape[0] == 2, f"edge_index {tuple(edge_index.shape)} must be [2, E]")
+        _shape(int(num_nodes) >= 0, f"num_nodes = {num_nodes}")
+        N = int(num_nodes)
+        # an index outside [0, N) would make the gathers / scatters read or write out of bounds: bit 1 of the flag, read back together with the
+        # sortedness bit (one device-to-host read, as before)
+        bad = ((edge_index < 0) | (edge_index >= N)).any()
+        if edge_index.device.type != "cuda" and bool(bad):
+            raise IndexError(f"edge_index holds a node index outside [0, {N})")
         _dev(edge_index)
         self.row = edge_index[0].to(torch.int64).contiguous()
         self.col = edge_index[1].to(torch.int64).contiguous()
-        self.N, self.E = int(num_nodes), int(self.row.shape[0])
+        self.N, self.E = N, int(self.row.shape[0])
         self.rowptr = torch.empty(self.N + 1, dtype=torch.int32, device=self.row.device)
         flag = torch.zeros(1, dtype=torch.int32, device=self.row.device)
         _chk(_lib().gcdm_op_rowptr(_p(self.row), self.E, self.N, _p(self.rowptr), _p(flag), _st(self.row)), "gcdm_op_rowptr")
-        if int(flag.item()) & 1:
+        flag |= bad.to(torch.int32) << 1
+        f = int(flag.item())
+        if f & 2:
+            raise IndexError(f"edge_index holds a node index outside [0, {N})")
+        if f & 1:
             raise ValueError("edge_index must be sorted by its first row (source node), as get_fully_connected_edge_index produces it")
 
 
@@ -276,6 +307,7 @@ def graph_of(edge_index: torch.Tensor, num_nodes: int) -> Graph:
 class _Gather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, graph, by_row):
+        _shape(x.dim() >= 1 and x.shape[0] == graph.N, f"gather: x {tuple(x.shape)} for a graph of {graph.N} nodes")
         xs = _f(x).reshape(x.shape[0], -1)
         idx = graph.row if by_row else graph.col
         out = torch.empty((graph.E, xs.shape[1]), dtype=torch.float32, device=xs.device)
@@ -301,11 +333,12 @@ class _Embedding(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, index):
-        w = _f(weight)
+        _shape(weight.dim() == 2, f"embedding: table {tuple(weight.shape)} must be [num, dim]")
         idx = index.reshape(-1).to(torch.int64).contiguous()
-        _dev(w)
-        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= w.shape[0]):
-            raise IndexError(f"embedding index out of range [0, {w.shape[0]})")
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= weight.shape[0]):
+            raise IndexError(f"embedding index out of range [0, {weight.shape[0]})")
+        w = _f(weight)
+        _dev(idx)
         out = torch.empty((idx.numel(), w.shape[1]), dtype=torch.float32, device=w.device)
         _chk(_lib().gcdm_op_gather(_p(w), _p(idx), _p(out), idx.numel(), w.shape[1], _st(w)), "gcdm_op_gather")
         ctx.idx, ctx.rows = idx, w.shape[0]
@@ -335,6 +368,7 @@ def gather_col(x: torch.Tensor, graph: Graph) -> torch.Tensor:
 class _SegmentReduce(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, graph, mean):
+        _shape(x.dim() >= 1 and x.shape[0] == graph.E, f"scatter_rows: x {tuple(x.shape)} for a graph of {graph.E} edges")
         xs = _f(x).reshape(x.shape[0], -1)
         out = torch.empty((graph.N, xs.shape[1]), dtype=torch.float32, device=xs.device)
         _chk(_lib().gcdm_op_segment_sum(_p(xs), _p(graph.rowptr), _p(out), graph.N, xs.shape[1], int(mean), _st(xs)), "gcdm_op_segment_sum")
@@ -359,6 +393,8 @@ def scatter_rows(x: torch.Tensor, graph: Graph, reduce: str = "sum") -> torch.Te
 
 def mean_frames(frames: torch.Tensor, graph: Graph, edge_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-node mean of the frames of its edges [N, 3, 3] (masked edges contribute zeros but count, as in the reference's scatter-mean)."""
+    _shape(frames.numel() == 9 * graph.E and frames.shape[0] == graph.E, f"mean_frames: frames {tuple(frames.shape)} for {graph.E} edges")
+    _shape(edge_mask is None or edge_mask.numel() == graph.E, f"mean_frames: edge_mask of {None if edge_mask is None else edge_mask.numel()} entries")
     f = _f(frames).reshape(-1, 9)
     if edge_mask is not None:
         f = f * edge_mask.to(f.dtype).unsqueeze(-1)
@@ -368,7 +404,28 @@ def mean_frames(frames: torch.Tensor, graph: Graph, edge_mask: Optional[torch.Te
 
 
 # ---- geometry of the network input (no gradients) -----------------------------------------------------------------------------------------
+def _geometry_shapes(x: torch.Tensor, edge_index: Optional[torch.Tensor], what: str) -> None:
+    _shape(x.dim() == 2 and x.shape[1] == 3, f"{what}: positions {tuple(x.shape)} must be [N, 3]")
+    _shape(edge_index is None or (edge_index.dim() == 2 and edge_index.shape[0] == 2), f"{what}: edge_index must be [2, E]")
+
+
+_RANGE_CACHE = {}
+
+
+def _node_range(edge_index: torch.Tensor, num_nodes: int, what: str) -> None:
+    """Refuses node indices outside [0, N) on the host before a kernel reads positions at them.  One device-to-host read per edge_index:
+    the last one that passed is remembered under the same key as graph_of (localize and edge_features of a forward share it)."""
+    key = (edge_index.data_ptr(), tuple(edge_index.shape), _native.tensor_version(edge_index), str(edge_index.device), int(num_nodes))
+    if _RANGE_CACHE.get("key") == key:
+        return
+    if edge_index.numel() and bool(((edge_index < 0) | (edge_index >= num_nodes)).any()):
+        raise IndexError(f"{what}: edge_index holds a node index outside [0, {num_nodes})")
+    _RANGE_CACHE["key"], _RANGE_CACHE["keep"] = key, edge_index
+
+
 def localize(x: torch.Tensor, edge_index: torch.Tensor, norm_x_diff: bool = True) -> torch.Tensor:
+    _geometry_shapes(x, edge_index, "localize")
+    _node_range(edge_index, x.shape[0], "localize")
     xs = _f(x)
     row, col = edge_index[0].to(torch.int64).contiguous(), edge_index[1].to(torch.int64).contiguous()
     E = int(row.shape[0])
@@ -378,6 +435,8 @@ def localize(x: torch.Tensor, edge_index: torch.Tensor, norm_x_diff: bool = True
 
 
 def edge_features(x: torch.Tensor, edge_index: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    _geometry_shapes(x, edge_index, "edge_features")
+    _node_range(edge_index, x.shape[0], "edge_features")
     xs = _f(x)
     row, col = edge_index[0].to(torch.int64).contiguous(), edge_index[1].to(torch.int64).contiguous()
     E = int(row.shape[0])
@@ -388,6 +447,7 @@ def edge_features(x: torch.Tensor, edge_index: torch.Tensor) -> Tuple[torch.Tens
 
 
 def orientations(x: torch.Tensor) -> torch.Tensor:
+    _geometry_shapes(x, None, "orientations")
     xs = _f(x)
     out = torch.empty((xs.shape[0], 2, 3), dtype=torch.float32, device=xs.device)
     _chk(_lib().gcdm_op_orientations(_p(xs), _p(out), xs.shape[0], _st(xs)), "gcdm_op_orientations")
@@ -415,6 +475,9 @@ class _Centralize(torch.autograd.Function):
 
 
 def centralize(x: torch.Tensor, batch_index: torch.Tensor, node_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _shape(x.dim() == 2, f"centralize: x {tuple(x.shape)} must be [N, D]")
+    _shape(batch_index.numel() == x.shape[0], f"centralize: batch_index of {batch_index.numel()} entries for {x.shape[0]} rows")
+    _shape(node_mask is None or node_mask.numel() == x.shape[0], f"centralize: node_mask of {None if node_mask is None else node_mask.numel()} entries")
     bi = batch_index.to(torch.int64).contiguous()
     mk = None if node_mask is None else node_mask.to(torch.uint8).contiguous()
     return _Centralize.apply(x, bi, mk)
@@ -423,6 +486,7 @@ def centralize(x: torch.Tensor, batch_index: torch.Tensor, node_mask: Optional[t
 def fully_connected_edge_index(num_nodes: torch.Tensor, device) -> torch.Tensor:
     """get_fully_connected_edge_index (gcpnet.py:1054-1066) from the molecule sizes: [2, sum n^2] int64, self-loops included, sorted."""
     nn_ = torch.as_tensor(num_nodes, dtype=torch.int64, device="cpu")
+    _shape(nn_.dim() == 1 and bool((nn_ >= 0).all()), f"fully_connected_edge_index: molecule sizes must be a list of counts >= 0, got {nn_.tolist()}")
     noff = torch.zeros(len(nn_) + 1, dtype=torch.int32)
     noff[1:] = torch.cumsum(nn_, 0).to(torch.int32)
     eoff = torch.zeros(len(nn_) + 1, dtype=torch.int64)

@@ -3,6 +3,13 @@
  * -1 for a bad argument, -2 if the launch failed.  All tensors fp32, row-major; index tensors int64 (torch's edge_index), CSR pointers
  * int32.  Work is enqueued on `stream`; nothing is allocated, nothing synchronises.
  *
+ * Bad arguments, checked before any HIP call (the call then returns -1 and touches nothing): a negative size (M, N, K, C, CH, KC, D, n,
+ * E, B); `kind` outside 0..5; `rep_layout`, `mean` or `norm_x_diff` outside {0, 1}; `slices` < 1; a null pointer the call reads or writes
+ * while its work is non-empty (gemm's `bias`, colsum's `dy` with M = 0 and centralize's `mask` may be null); fc_edges with B = 0 and E > 0.
+ * Empty work (nothing to write) returns 0 without a launch; rowptr is never empty (it writes N + 1 entries).  Index VALUES are not checked
+ * here: the caller keeps them in range (ops.Graph, ops.embedding, ops.localize and ops.edge_features refuse out-of-range indices before
+ * a launch).
+ *
  * What each entry replaces in the reference (BioinfoMachineLearning/bio-diffusion, src/models/components/):
  *   gcdm_op_gemm            every nn.Linear of GCP / GCP2 (gcpnet.py:85-118, 320-348) and its autograd: y = x W^T + b, dx = dy W, dW = dy^T x
  *   gcdm_op_colsum[_slices] the bias gradient of those Linears (with many rows: partial sums over row slices on the whole chip + gcdm_op_reduce_slices)
