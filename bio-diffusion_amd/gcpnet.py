@@ -13,6 +13,7 @@ gradient is being recorded.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Any, Optional, Tuple
 
@@ -322,11 +323,8 @@ class GCPNetDynamics(nn.Module):
             # one host sync to make the module-level call self-healing (the fused sampler loop reads the flag once per run instead):
             # an activation beyond the f16 range -> recompute this call with fp32 MFMA
             if self.read_flags() & _native.FLAG_F16_RANGE:
-                self.set_mfma_mode(0)
-                try:
+                with self.fp32_mfma():
                     out = self.native_forward(xh, t, ctx, xh_self_cond=sc)
-                finally:
-                    self.set_mfma_mode(1)
         return batch, out
 
     def check_deferred_flags(self, wait: bool = True) -> int:
@@ -356,6 +354,16 @@ class GCPNetDynamics(nn.Module):
     def set_mfma_mode(self, mode: int) -> None:
         """0: fp32 MFMA everywhere; 1: split-precision f16x3 edge kernel (fp32-equivalent accuracy, default)."""
         _native.check(self._lib, self._handle, self._lib.gcdm_set_option(self._handle, b"mfma_mode", int(mode)), "gcdm_set_option")
+
+    @contextlib.contextmanager
+    def fp32_mfma(self):
+        """fp32 MFMA for the calls inside (a re-run after an f16-range overflow); the handle returns to the split-precision default (mode 1)
+        afterwards, also when they raise."""
+        self.set_mfma_mode(0)
+        try:
+            yield
+        finally:
+            self.set_mfma_mode(1)
 
     def native_forward(self, xh: torch.Tensor, t: torch.Tensor, context: Optional[torch.Tensor] = None,
                        out: Optional[torch.Tensor] = None, xh_self_cond: Optional[torch.Tensor] = None) -> torch.Tensor:

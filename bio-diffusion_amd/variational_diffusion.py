@@ -164,48 +164,109 @@ class NumNodesDistribution(nn.Module):
 RANGE_CHECK_EVERY = 25          # steps between two looks at the f16-range flag inside the fused sampling loops
 
 
-class _RangeCheckpoints:
-    """Range guard of the split-precision mode INSIDE a sampling loop.  Every RANGE_CHECK_EVERY steps the loop hands over a snapshot of its
-    state (latent + counters) together with an asynchronous copy of the device flag word; one interval later that copy has long arrived and
-    is looked at without stalling the GPU: clean -> the snapshot becomes the restart point; GCDM_FLAG_F16_RANGE -> the loop resumes from the
-    previous restart point with fp32 MFMA instead of re-running the whole trajectory (an overflow at step 900 of 1000 costs <= 1.3x a
-    clean run; it used to cost 1 + 2.7)."""
+def _pinned_flag_copy(flags: torch.Tensor) -> Callable[[], List[int]]:
+    """Asynchronous copy of the device flag word(s) to pinned host memory, on the current stream; returns the reader that waits for it."""
+    host = torch.zeros(flags.numel(), dtype=torch.int32).pin_memory()
+    host.copy_(flags, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(flags.device))
 
-    def __init__(self, device):
-        self.device = device
+    def read() -> List[int]:
+        ev.synchronize()
+        return [int(v) for v in host.tolist()]
+    return read
+
+
+class _RangeCheckpoints:
+    """Range guard of the split-precision mode INSIDE a sampling loop, and the loop itself (``run``).  Every RANGE_CHECK_EVERY steps the loop
+    hands over a snapshot of its state (latent + counters) together with an asynchronous copy of the device flag word; one interval later
+    that copy has long arrived and is looked at without stalling the GPU: clean -> the snapshot becomes the restart point;
+    GCDM_FLAG_F16_RANGE -> the loop resumes from the previous restart point with fp32 MFMA instead of re-running the whole trajectory (an
+    overflow at step 900 of 1000 costs <= 1.3x a clean run; it used to cost 1 + 2.7).  ``active=False`` (the handle already runs fp32 MFMA):
+    the plain loop.  ``copy_flags(flags)`` starts the flag copy and returns its reader (default: pinned copy + event)."""
+
+    def __init__(self, active: bool = True, copy_flags: Callable[[torch.Tensor], Callable[[], List[int]]] = _pinned_flag_copy):
+        self.active = active
+        self.copy_flags = copy_flags
         self.good = None             # (state, tensors) verified clean
-        self.pend = None             # (state, tensors, event, host flag) waiting for its flag copy
+        self.pend = None             # (state, tensors, reader of the flag copy) waiting for its flag copy
         self.rewinds = 0
-        self.tail_flag = False       # GCDM_FLAG_TAIL seen (comes together with GCDM_FLAG_F16_RANGE: the rewind repairs the trajectory)
+        self.fell_back = False       # the handle was switched to fp32 MFMA at step resume_step
+        self.resume_step = None
+        self.tail_flag = False       # GCDM_FLAG_TAIL in any flag word looked at (the caller disables the fused layer launch)
+
+    def run(self, num_timesteps: int, step: Callable[[int], None], final: Callable[[], int], flags: torch.Tensor,
+            save: Callable[[], Tuple[Dict[str, Any], List[torch.Tensor]]], load: Callable[[Dict[str, Any], List[torch.Tensor]], None],
+            set_mode: Callable[[int], None], wait: Callable[[], None] = lambda: None, fence: Callable[[], None] = lambda: None) -> int:
+        """Steps s = num_timesteps - 1 ... 0, then the final decode; returns its flag word (the caller reports it).  ``step(s)`` / ``final()``
+        enqueue the work (``final`` reads the flag word: the one host sync of a clean run); ``save()`` -> (counters, latent tensors) and
+        ``load(counters, copies)`` put a snapshot back; ``set_mode(m)`` switches the handle(s) between fp32 (0) and split-precision (1) MFMA;
+        ``wait()`` / ``fence()`` order the caller's stream after / before the work around a snapshot or restore (several streams)."""
+        def restart(point):
+            st, copies = point
+            wait()
+            load(st, copies)
+            self.restore_flags(flags, st)
+            if not self.fell_back:
+                log.warning("An activation left the f16 range of the split-precision kernels; resuming from step %d with fp32 MFMA.", st["s"])
+                set_mode(0)
+                self.fell_back, self.resume_step = True, st["s"]
+            fence()
+            return st["s"]
+
+        try:
+            s = num_timesteps - 1
+            if self.active:
+                wait()
+                st, tensors = save()
+                self.good = (dict(st, s=s), [t.clone() for t in tensors])
+                fence()
+            while True:
+                while s >= 0:
+                    if self.active and not self.fell_back and (num_timesteps - 1 - s) % RANGE_CHECK_EVERY == 0 and s != num_timesteps - 1:
+                        wait()
+                        st, tensors = save()
+                        point = self.snapshot(dict(st, s=s), tensors, flags)
+                        fence()
+                        if point is not None:
+                            s = restart(point)
+                            continue
+                    step(s)
+                    s -= 1
+                fl = final()
+                point = self.resolve(fl) if (self.active and not self.fell_back) else None
+                if point is None:
+                    return fl
+                s = restart(point)       # an overflow in the last interval (or in the decode): repeat it in fp32
+        finally:
+            if self.fell_back:
+                set_mode(1)
 
     def snapshot(self, state: Dict[str, Any], tensors: List[torch.Tensor], flags: torch.Tensor):
         """Called on the stream the latent is valid on.  Returns the restart point to rewind to if the PREVIOUS snapshot's flag is dirty."""
         rewind = self.resolve()
         if rewind is not None:
             return rewind
-        host = torch.zeros(flags.numel(), dtype=torch.int32).pin_memory()
         copies = [t.clone() for t in tensors]
-        host.copy_(flags, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self.pend = (dict(state), copies, ev, host)
+        self.pend = (dict(state), copies, self.copy_flags(flags))
         return None
 
     def resolve(self, final_flags: Optional[int] = None):
         """Looks at the pending snapshot's flag copy (or, at the end of the run, at the final flag word).  Returns (state, tensors) to rewind
         to, or None if the trajectory so far is clean."""
         if self.pend is not None:
-            st, copies, ev, host = self.pend
-            ev.synchronize()
-            dirty = any(int(v) & _native.FLAG_F16_RANGE for v in host.tolist())
-            self.tail_flag |= any(int(v) & _native.FLAG_TAIL for v in host.tolist())      # (fused layer launch; the caller of resolve() disables it on its handle)
+            st, copies, read = self.pend
+            host = read()
             self.pend = None
-            if dirty:
+            self.tail_flag |= any(v & _native.FLAG_TAIL for v in host)
+            if any(v & _native.FLAG_F16_RANGE for v in host):
                 return self._rewind()
-            st["flags"] = [int(v) for v in host.tolist()]      # the flag word(s) AT the snapshot: what a rewind restores (bits raised during a
+            st["flags"] = host                                 # the flag word(s) AT the snapshot: what a rewind restores (bits raised during a
             self.good = (st, copies)                           # discarded f16 interval -- NaN in vel, CoG drift -- must not survive it)
-        if final_flags is not None and final_flags & _native.FLAG_F16_RANGE:
-            return self._rewind()
+        if final_flags is not None:
+            self.tail_flag |= bool(final_flags & _native.FLAG_TAIL)
+            if final_flags & _native.FLAG_F16_RANGE:
+                return self._rewind()
         return None
 
     def _rewind(self):
@@ -220,7 +281,7 @@ class _RangeCheckpoints:
         if saved is not None:
             flags.copy_(torch.tensor(saved, dtype=flags.dtype).to(flags.device, non_blocking=True))
         else:
-            flags.bitwise_and_(~(_native.FLAG_F16_RANGE | _native.FLAG_NAN_VEL | _native.FLAG_COG_DRIFT))
+            flags.bitwise_and_(~(_native.FLAG_F16_RANGE | _native.FLAG_NAN_VEL | _native.FLAG_COG_DRIFT | _native.FLAG_TAIL))
 
 
 class _Batch(AttrDict):
@@ -246,6 +307,8 @@ class EquivariantVariationalDiffusion(nn.Module):
         self.gamma = PredefinedNoiseSchedule(noise_schedule=cfg_get(diffusion_cfg, "noise_schedule"), num_timesteps=self.T,
                                              noise_precision=float(cfg_get(diffusion_cfg, "noise_precision")))
         self._gamma_uploaded = None
+        # outcome of the last sampling call: device flag word, range rewinds, step an fp32 resume started from
+        self.last_flags, self.last_range_rewinds, self.last_range_resume_step = 0, 0, None
 
     # ---- schedule algebra (:318-367) ---------------------------------------------------------------
     @staticmethod
@@ -453,13 +516,7 @@ class EquivariantVariationalDiffusion(nn.Module):
                 b = self.dynamics_network(batch, z_0, t_zeros[bi], xh_self_cond=None, **self._deferred())[1]
                 self._final_range_check()
                 return a, b
-            try:
-                net_out, net_out_0 = two_evaluations()
-            except F16RangeError:           # an activation left the f16 images: the handle now runs fp32 MFMA, same inputs again
-                try:
-                    net_out, net_out_0 = two_evaluations()
-                finally:                    # ... and returns to its default mode: one overflowing batch must not slow every later call
-                    self.dynamics_network.set_mfma_mode(1)
+            net_out, net_out_0 = self._rerun_in_fp32(two_evaluations, "the network evaluations")
             error_t = self.sum_node_features_except_batch((eps_t - net_out) ** 2, bi, B)
             SNR_weight = (self.SNR(gamma_s - gamma_t) - 1).squeeze(-1)
             log_px, log_ph = self.log_pxh_given_z0_without_constants(h=h, z_0=z_0, eps=eps_0, net_out=net_out_0, gamma_0=gamma_0, batch_index=bi,
@@ -556,6 +613,39 @@ class EquivariantVariationalDiffusion(nn.Module):
         if chk is not None:
             chk(wait=True)
 
+    def _rerun_in_fp32(self, fn: Callable[[], Any], what: str) -> Any:
+        """``fn()``; on F16RangeError (an activation left the f16 range of the split-precision kernels) ``fn()`` once more with fp32 MFMA --
+        ``fn`` must draw the same noise again -- after which the handle returns to its default mode and ``last_flags`` reports FLAG_F16_RANGE."""
+        try:
+            return fn()
+        except F16RangeError:
+            log.warning("An activation left the f16 range of the split-precision kernels; re-running %s with fp32 MFMA.", what)
+        with self.dynamics_network.fp32_mfma():
+            out = fn()
+        self.last_flags |= _native.FLAG_F16_RANGE
+        return out
+
+    def _report_flags(self, fl: int, where: str, guard: Optional[_RangeCheckpoints] = None) -> int:
+        """The final device flag word of a fused sampling run -> ``last_flags`` / ``last_range_rewinds`` / ``last_range_resume_step``, warnings
+        and errors.  A run whose guard fell back to fp32 MFMA reports FLAG_F16_RANGE."""
+        if fl & _native.FLAG_F16_RANGE:
+            raise RuntimeError("f16 range flag raised in fp32 mode (internal error)")
+        fell_back = guard is not None and guard.fell_back
+        if fell_back:
+            fl |= _native.FLAG_F16_RANGE
+        self.last_range_rewinds = 0 if guard is None else guard.rewinds
+        self.last_range_resume_step = guard.resume_step if fell_back else None
+        if fl & _native.FLAG_TAIL or (guard is not None and guard.tail_flag):
+            self.dynamics_network.disable_fused_layer(where)      # (the affected interval was repeated with two launches per layer by the range rewind)
+        if fl & _native.FLAG_MEAN_NOT_ZERO:
+            raise AssertionError("Mean is not zero: the supplied samples are not centred (assert_mean_zero_with_mask, relative error >= 1e-2)")
+        if fl & _native.FLAG_NAN_VEL:
+            log.warning("Detected NaN in `vel` -> GCPNet `vel` output was reset to zero for at least one time step.")
+        if fl & _native.FLAG_COG_DRIFT:
+            log.warning("CoG drift above 5e-2. Projected the positions down.")
+        self.last_flags = fl
+        return fl
+
     # ---- production loop (:1282-1412) ---------------------------------------------------------------
     def _native(self, device):
         dyn = self.dynamics_network
@@ -571,31 +661,12 @@ class EquivariantVariationalDiffusion(nn.Module):
         return dyn, lib, h
 
     def _mol_gen_sample_modules(self, num_samples, num_nodes, device, return_frames, num_timesteps, node_mask, context, fix_noise,
-                                fix_self_conditioning_noise, norm_with_original_timesteps, noise_fn, step_callback, generate_x_only: bool = False,
-                                seed: int = 1234, init_xh: Optional[torch.Tensor] = None):
+                                fix_self_conditioning_noise, norm_with_original_timesteps, noise_fn, step_callback, generate_x_only, seed, init_xh):
         """mol_gen_sample (:1282-1412) step by step through the reference-signature methods of this class -- torch algebra on the device around
         one network evaluation per step on whichever HIP path the configuration / mask selects.  Serves masked nodes inside the loop and the
         configurations the fused sampling kernels are not built for; ~10x slower per step than the fused loop.  ``noise_fn(k)``: raw draw k;
-        without it the draws come from a device torch.Generator seeded with ``seed`` (reproducible per seed, in the reference's randn order).
-        An activation beyond the f16 range of the split-precision kernels (F16RangeError of the deferred guard; the handle is then in fp32
-        MFMA) re-runs the loop from z_T on the same noise, and the handle returns to its default mode afterwards."""
-        dyn = self.dynamics_network
-        try:
-            return self._mol_gen_sample_modules_once(num_samples, num_nodes, device, return_frames, num_timesteps, node_mask, context, fix_noise,
-                                                     fix_self_conditioning_noise, norm_with_original_timesteps, noise_fn, step_callback, generate_x_only, seed, init_xh)
-        except F16RangeError:
-            log.warning("An activation left the f16 range of the split-precision kernels; re-running the sampling loop with fp32 MFMA.")
-            try:
-                out = self._mol_gen_sample_modules_once(num_samples, num_nodes, device, return_frames, num_timesteps, node_mask, context, fix_noise,
-                                                        fix_self_conditioning_noise, norm_with_original_timesteps, noise_fn, step_callback, generate_x_only, seed, init_xh)
-            finally:
-                if getattr(dyn, "_handle", None) is not None:
-                    dyn.set_mfma_mode(1)
-            self.last_flags = _native.FLAG_F16_RANGE          # reported: this sample was computed with fp32 MFMA
-            return out
-
-    def _mol_gen_sample_modules_once(self, num_samples, num_nodes, device, return_frames, num_timesteps, node_mask, context, fix_noise,
-                                     fix_self_conditioning_noise, norm_with_original_timesteps, noise_fn, step_callback, generate_x_only, seed, init_xh=None):
+        without it the draws come from a device torch.Generator seeded with ``seed`` (reproducible per seed, in the reference's randn order,
+        so that a re-run after F16RangeError draws the same noise)."""
         num_timesteps = self.T if num_timesteps is None else num_timesteps
         assert 0 < return_frames <= num_timesteps, "Number of frames cannot be greater than number of timesteps."
         assert num_timesteps % return_frames == 0, "Number of frames must be evenly divisible by number of timesteps."
@@ -674,29 +745,28 @@ class EquivariantVariationalDiffusion(nn.Module):
                        context: Optional[torch.Tensor] = None, fix_noise: bool = False, generate_x_only: bool = False,
                        fix_self_conditioning_noise: bool = False, norm_with_original_timesteps: bool = False,
                        noise_fn: Optional[Callable[[int], torch.Tensor]] = None, seed: int = 1234,
-                       step_callback: Optional[Callable[[int, torch.Tensor], None]] = None, _retry_fp32: bool = False,
+                       step_callback: Optional[Callable[[int, torch.Tensor], None]] = None,
                        _init_xh: Optional[torch.Tensor] = None, _t_norm: Optional[int] = None, lanes: int = 1
                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Draw samples.  ``noise_fn(k)`` (optional) returns the k-th raw standard-normal draw [N,3+F] on ``device``
         (k = 0 for z_T, then one per step, then one for the final decode: the reference's randn call order,
         SURVEY A.5); without it noise comes from on-device Philox(seed)."""
-        if generate_x_only:
-            # position-only diffusion (:1292, 1325-1327, 1349, 1385, 1407-1408): z = z_x, every draw is the centred x-noise alone, the result is the
-            # [N, 3] positions.  It needs a dynamics network built WITHOUT node features (dataloader_cfg.num_atom_types = 0, include_charges = False:
-            # xh is [N, 3] then, as in the reference) -- the general loop on the module path.
-            if getattr(self.dynamics_network, "num_atom_types", 0) + int(getattr(self.dynamics_network, "include_charges", False)) > 0:
-                raise ValueError("generate_x_only needs a dynamics network built without node features (num_atom_types = 0, include_charges = False); "
-                                 "the reference fails on the feature width of this one too (gcpnet.py:1093-1110)")
-            return self._mol_gen_sample_modules(num_samples, num_nodes, device, return_frames, num_timesteps, node_mask, context, fix_noise,
-                                                fix_self_conditioning_noise, norm_with_original_timesteps, noise_fn, step_callback, generate_x_only=True, seed=seed)
-        masked = node_mask is not None and not bool(node_mask.all())
-        if masked or getattr(self.dynamics_network, "fused_unsupported", None) is not None or getattr(self.dynamics_network, "path", "auto") == "modules":
-            # general loop: masked nodes inside the loop, or a configuration the fused sampling kernels are not built for
+        # position-only diffusion (:1292, 1325-1327, 1349, 1385, 1407-1408): z = z_x, every draw is the centred x-noise alone, the result is the
+        # [N, 3] positions.  It needs a dynamics network built WITHOUT node features (dataloader_cfg.num_atom_types = 0, include_charges = False:
+        # xh is [N, 3] then, as in the reference) -- the general loop on the module path.
+        if generate_x_only and getattr(self.dynamics_network, "num_atom_types", 0) + int(getattr(self.dynamics_network, "include_charges", False)) > 0:
+            raise ValueError("generate_x_only needs a dynamics network built without node features (num_atom_types = 0, include_charges = False); "
+                             "the reference fails on the feature width of this one too (gcpnet.py:1093-1110)")
+        if (generate_x_only or (node_mask is not None and not bool(node_mask.all()))
+                or getattr(self.dynamics_network, "fused_unsupported", None) is not None or getattr(self.dynamics_network, "path", "auto") == "modules"):
+            # general loop: position-only diffusion, masked nodes inside the loop, or a configuration the fused sampling kernels are not built for
             if _t_norm is not None:
                 raise NotImplementedError("an explicit time normalisation runs on the fused path only")
-            return self._mol_gen_sample_modules(num_samples, num_nodes, torch.device(device), return_frames, num_timesteps, node_mask, context,
-                                                fix_noise, fix_self_conditioning_noise, norm_with_original_timesteps, noise_fn, step_callback, seed=seed,
-                                                init_xh=_init_xh)
+            return self._rerun_in_fp32(lambda: self._mol_gen_sample_modules(num_samples, num_nodes, torch.device(device), return_frames, num_timesteps,
+                                                                            node_mask, context, fix_noise, fix_self_conditioning_noise,
+                                                                            norm_with_original_timesteps, noise_fn, step_callback, generate_x_only, seed,
+                                                                            _init_xh),
+                                       "the sampling loop")
         self_cond_on = bool(getattr(self.dynamics_network, "self_condition", False))
         if fix_noise or self_cond_on:
             lanes = 1                  # fix_noise: the noise is centred over the whole flat batch; self-conditioning: not sliced (yet)
@@ -709,7 +779,7 @@ class EquivariantVariationalDiffusion(nn.Module):
         t_norm = _t_norm if _t_norm is not None else (self.T if norm_with_original_timesteps else num_timesteps)
         if num_timesteps > t_norm:
             raise ValueError("num_timesteps exceeds the normalising number of timesteps")
-        if lanes > 1 and not _retry_fp32 and len(num_nodes) >= 2 * lanes and not (
+        if lanes > 1 and len(num_nodes) >= 2 * lanes and not (
                 noise_fn is not None or return_frames != 1 or _init_xh is not None or step_callback is not None):
             # slices of the flat batch on several handles / streams: plain sampling with on-device noise; anything else runs on one handle
             return self._mol_gen_sample_lanes(num_samples, num_nodes, device, num_timesteps, t_norm, context, seed, lanes)
@@ -755,92 +825,53 @@ class EquivariantVariationalDiffusion(nn.Module):
             _native.check(lib, h, lib.gcdm_encode_samples(h, C.c_void_p(xin.data_ptr()), C.c_void_p(z.data_ptr()), fptr, stream),
                           "gcdm_encode_samples")
         self_cond = torch.zeros_like(z) if self_cond_on else None     # the estimate fed back into the next step (:1363-1375)
-        guard = _RangeCheckpoints(device) if (dyn.mfma_mode == 1 and not _retry_fp32) else None
-        fell_back = False
+        latent = [z] + ([self_cond] if self_cond_on else [])
 
-        def restart(point):
-            """Resume from a clean snapshot with fp32 MFMA (the f16-range flag was raised after it)."""
-            nonlocal k, fell_back
-            st0, (z0, *rest) = point
-            z.copy_(z0)
+        def step(s):
+            keep, p = nptr()
             if self_cond_on:
-                self_cond.copy_(rest[0])
-            k = st0["k"]
-            _RangeCheckpoints.restore_flags(flags, st0)
-            if not fell_back:
-                log.warning("An activation left the f16 range of the split-precision kernels; resuming from step %d with fp32 MFMA.", st0["s"])
-                dyn.set_mfma_mode(0)
-                fell_back = True
-                self.last_range_resume_step = st0["s"]
-            return st0["s"]
+                keep2, p2 = nptr()
+                st = lib.gcdm_sample_step_sc(h, C.c_void_p(z.data_ptr()), C.c_void_p(self_cond.data_ptr()), int(s != num_timesteps - 1), ctx_ptr, s, t_norm,
+                                             p, p2, C.c_uint64(seed), fptr, stream)
+            else:
+                st = lib.gcdm_sample_step(h, C.c_void_p(z.data_ptr()), ctx_ptr, s, t_norm, p, C.c_uint64(seed), fptr, stream)
+            _native.check(lib, h, st, "gcdm_sample_step")
+            if return_frames > 1 and (s * return_frames) % num_timesteps == 0:             # save frame (:1354-1361)
+                fr = frames[(s * return_frames) // num_timesteps]
+                _native.check(lib, h, lib.gcdm_unnormalize_z(h, C.c_void_p(z.data_ptr()), C.c_void_p(fr.data_ptr()), stream), "gcdm_unnormalize_z")
+            if step_callback is not None:
+                step_callback(s, z)              # (fires again for the steps a resumed run repeats)
 
+        def final():
+            keep, p = nptr()
+            _native.check(lib, h, lib.gcdm_set_option(h, b"cog_fix", 1 if return_frames == 1 else 0), "gcdm_set_option")   # :1389
+            if self_cond_on:
+                st = lib.gcdm_sample_final_sc(h, C.c_void_p(z.data_ptr()), C.c_void_p(self_cond.data_ptr()) if num_timesteps > 0 else None, ctx_ptr, p,
+                                              C.c_uint64(seed), C.c_void_p(out.data_ptr()), fptr, stream)
+            else:
+                st = lib.gcdm_sample_final(h, C.c_void_p(z.data_ptr()), ctx_ptr, p, C.c_uint64(seed), C.c_void_p(out.data_ptr()), fptr, stream)
+            lib.gcdm_set_option(h, b"cog_fix", 1)
+            _native.check(lib, h, st, "gcdm_sample_final")
+            return int(flags.item())             # the one host sync of a clean run
+
+        def load(st, copies):
+            nonlocal k
+            for t_, c_ in zip(latent, copies):
+                t_.copy_(c_)
+            k = st["k"]
+
+        guard = _RangeCheckpoints(active=dyn.mfma_mode == 1)
         try:
-            s = num_timesteps - 1
-            first = {"s": s, "k": k}
-            if guard is not None:
-                guard.good = (first, [z.clone()] + ([self_cond.clone()] if self_cond_on else []))
-            while True:
-                while s >= 0:
-                    if guard is not None and not fell_back and (num_timesteps - 1 - s) % RANGE_CHECK_EVERY == 0 and s != num_timesteps - 1:
-                        point = guard.snapshot({"s": s, "k": k}, [z] + ([self_cond] if self_cond_on else []), flags)
-                        if point is not None:
-                            s = restart(point)
-                            continue
-                    keep, p = nptr()
-                    if self_cond_on:
-                        keep2, p2 = nptr()
-                        st = lib.gcdm_sample_step_sc(h, C.c_void_p(z.data_ptr()), C.c_void_p(self_cond.data_ptr()), int(s != num_timesteps - 1), ctx_ptr, s, t_norm,
-                                                     p, p2, C.c_uint64(seed), fptr, stream)
-                    else:
-                        st = lib.gcdm_sample_step(h, C.c_void_p(z.data_ptr()), ctx_ptr, s, t_norm, p, C.c_uint64(seed), fptr, stream)
-                    _native.check(lib, h, st, "gcdm_sample_step")
-                    if return_frames > 1 and (s * return_frames) % num_timesteps == 0:             # save frame (:1354-1361)
-                        fr = frames[(s * return_frames) // num_timesteps]
-                        _native.check(lib, h, lib.gcdm_unnormalize_z(h, C.c_void_p(z.data_ptr()), C.c_void_p(fr.data_ptr()), stream), "gcdm_unnormalize_z")
-                    if step_callback is not None:
-                        step_callback(s, z)              # (fires again for the steps a resumed run repeats)
-                    s -= 1
-                keep, p = nptr()
-                _native.check(lib, h, lib.gcdm_set_option(h, b"cog_fix", 1 if return_frames == 1 else 0), "gcdm_set_option")   # :1389
-                if self_cond_on:
-                    st = lib.gcdm_sample_final_sc(h, C.c_void_p(z.data_ptr()), C.c_void_p(self_cond.data_ptr()) if num_timesteps > 0 else None, ctx_ptr, p,
-                                                  C.c_uint64(seed), C.c_void_p(out.data_ptr()), fptr, stream)
-                else:
-                    st = lib.gcdm_sample_final(h, C.c_void_p(z.data_ptr()), ctx_ptr, p, C.c_uint64(seed), C.c_void_p(out.data_ptr()), fptr, stream)
-                lib.gcdm_set_option(h, b"cog_fix", 1)
-                _native.check(lib, h, st, "gcdm_sample_final")
-                fl = int(flags.item())   # the one host sync of a clean run
-                point = guard.resolve(fl) if (guard is not None and not fell_back) else None
-                if point is None:
-                    break
-                s = restart(point)       # an overflow in the last interval (or in the decode): repeat it in fp32
+            fl = guard.run(num_timesteps, step, final, flags, lambda: ({"k": k}, latent), load, dyn.set_mfma_mode)
         finally:
             lib.gcdm_set_option(h, b"fix_noise", 0)
-            if fell_back:
-                dyn.set_mfma_mode(1)
-        if fl & _native.FLAG_F16_RANGE:
-            raise RuntimeError("f16 range flag raised in fp32 mode (internal error)")
-        if fell_back:
-            fl |= _native.FLAG_F16_RANGE          # reported in last_flags: part of this sample was computed with fp32 MFMA
-        self.last_range_rewinds = 0 if guard is None else guard.rewinds
-        if guard is not None and (guard.tail_flag or (fl & _native.FLAG_TAIL)):
-            dyn.disable_fused_layer("mol_gen_sample")      # (the affected interval was repeated with two launches per layer by the range rewind)
-        if not fell_back:
-            self.last_range_resume_step = None
-        if fl & _native.FLAG_MEAN_NOT_ZERO:
-            raise AssertionError("Mean is not zero: the supplied samples are not centred (assert_mean_zero_with_mask, relative error >= 1e-2)")
-        if fl & _native.FLAG_NAN_VEL:
-            log.warning("Detected NaN in `vel` -> GCPNet `vel` output was reset to zero for at least one time step.")
-        if fl & _native.FLAG_COG_DRIFT:
-            log.warning("CoG drift above 5e-2. Projected the positions down.")
-        self.last_flags = fl
+        self._report_flags(fl, "mol_gen_sample", guard)
         return (out if return_frames == 1 else frames), batch_index, node_mask
 
     @torch.inference_mode()
     def inpaint(self, molecule: Dict[str, Any], node_mask_fixed: torch.Tensor, num_resamplings: int = 1, jump_length: int = 1,
                 return_frames: int = 1, num_timesteps: Optional[int] = None, context: Optional[torch.Tensor] = None,
-                generate_x_only: bool = False, noise_fn: Optional[Callable[[int], torch.Tensor]] = None, seed: int = 1234,
-                _retry_fp32: bool = False) -> torch.Tensor:
+                generate_x_only: bool = False, noise_fn: Optional[Callable[[int], torch.Tensor]] = None, seed: int = 1234) -> torch.Tensor:
         """Draw samples while keeping parts of the given molecules fixed (RePaint; variational_diffusion.py:1582-1789).
         ``molecule``: dict with "x" [N,3], "one_hot" [N,F], "charges" [N,1] (if the model has charges), "num_nodes" [B] (and optionally
         "batch_index", which must be the contiguous one); ``node_mask_fixed`` [N] bool.  Returns [N,3+F], or [return_frames,N,3+F].
@@ -854,8 +885,15 @@ class EquivariantVariationalDiffusion(nn.Module):
         if (generate_x_only or getattr(self.dynamics_network, "fused_unsupported", None) is not None
                 or getattr(self.dynamics_network, "path", "auto") == "modules"):
             # position-only diffusion (a dynamics network without node features) and configurations off the fused kernels: the general loop
-            return self._inpaint_modules(molecule, node_mask_fixed, num_resamplings, jump_length, return_frames, num_timesteps, context,
-                                         generate_x_only, noise_fn, seed)
+            return self._rerun_in_fp32(lambda: self._inpaint_modules(molecule, node_mask_fixed, num_resamplings, jump_length, return_frames,
+                                                                     num_timesteps, context, generate_x_only, noise_fn, seed),
+                                       "the inpainting loop")
+        return self._rerun_in_fp32(lambda: self._inpaint_fused_once(molecule, node_mask_fixed, num_resamplings, jump_length, return_frames,
+                                                                    num_timesteps, context, noise_fn, seed),
+                                   "the inpainting")
+
+    def _inpaint_fused_once(self, molecule, node_mask_fixed, num_resamplings, jump_length, return_frames, num_timesteps, context, noise_fn, seed):
+        """inpaint on the fused kernels, one run.  Raises F16RangeError if an activation left the f16 range of the split-precision kernels."""
         num_nodes = torch.as_tensor(molecule["num_nodes"])
         device = torch.device(molecule["x"].device)
         dyn, lib, h = self._native(device)
@@ -870,7 +908,7 @@ class EquivariantVariationalDiffusion(nn.Module):
         fixed = node_mask_fixed.to(device).bool().contiguous()
         if xh0.shape != (N, D) or fixed.shape != (N,):
             raise ValueError(f"molecule has shape {tuple(xh0.shape)} / mask {tuple(fixed.shape)}, expected {(N, D)} / {(N,)}")
-        ctx_ptr, context_in = None, context
+        ctx_ptr = None
         if context is not None:
             context = context.to(device, torch.float32)[batch_index].contiguous()
             ctx_ptr = C.c_void_p(context.data_ptr())
@@ -928,21 +966,11 @@ class EquivariantVariationalDiffusion(nn.Module):
         _native.check(lib, h, st, "gcdm_sample_final")
         fl = int(flags.item())                                                  # the one host sync of the run
         held.clear()
-        if fl & _native.FLAG_F16_RANGE:
-            if _retry_fp32:
-                raise RuntimeError("f16 range flag raised in fp32 mode (internal error)")
-            log.warning("An activation left the f16 range of the split-precision kernels; re-running the inpainting with fp32 MFMA.")
-            dyn.set_mfma_mode(0)
-            try:
-                return self.inpaint(molecule, node_mask_fixed, num_resamplings, jump_length, return_frames, num_timesteps, context_in,
-                                    generate_x_only, noise_fn=noise_fn, seed=seed, _retry_fp32=True)
-            finally:
-                dyn.set_mfma_mode(1)
-        if fl & _native.FLAG_NAN_VEL:
-            log.warning("Detected NaN in `vel` -> GCPNet `vel` output was reset to zero for at least one time step.")
-        if fl & _native.FLAG_COG_DRIFT:
-            log.warning("CoG drift above 5e-2. Projected the positions down.")
-        self.last_flags = fl
+        if fl & _native.FLAG_F16_RANGE and dyn.mfma_mode == 1:
+            if fl & _native.FLAG_TAIL:
+                dyn.disable_fused_layer("inpaint")
+            raise F16RangeError("an activation left the f16 range of the split-precision kernels during inpainting")
+        self._report_flags(fl, "inpaint")
         return out if return_frames == 1 else frames
 
     def sample_p_zt_given_zs(self, zs, batch_index, node_mask, gamma_t, gamma_s, generate_x_only: bool = False, noise: Optional[torch.Tensor] = None,
@@ -962,31 +990,12 @@ class EquivariantVariationalDiffusion(nn.Module):
         return zx if generate_x_only else torch.cat([zx, zt[:, self.num_x_dims:]], dim=-1)
 
     def _inpaint_modules(self, molecule, node_mask_fixed, num_resamplings, jump_length, return_frames, num_timesteps, context, generate_x_only,
-                         noise_fn, seed):
-        """_inpaint_modules_once with the range recovery of _mol_gen_sample_modules: an activation beyond the f16 range of the split-precision kernels
-        (F16RangeError of the deferred guard; the handle is then in fp32 MFMA) re-runs the loop from the start on the same noise (the draws are
-        indexed / seeded inside the loop), the handle returns to its default mode, and ``last_flags`` reports FLAG_F16_RANGE."""
-        dyn = self.dynamics_network
-        try:
-            return self._inpaint_modules_once(molecule, node_mask_fixed, num_resamplings, jump_length, return_frames, num_timesteps, context, generate_x_only,
-                                              noise_fn, seed)
-        except F16RangeError:
-            log.warning("An activation left the f16 range of the split-precision kernels; re-running the inpainting loop with fp32 MFMA.")
-            try:
-                out = self._inpaint_modules_once(molecule, node_mask_fixed, num_resamplings, jump_length, return_frames, num_timesteps, context, generate_x_only,
-                                                 noise_fn, seed)
-            finally:
-                if getattr(dyn, "_handle", None) is not None:
-                    dyn.set_mfma_mode(1)
-            self.last_flags |= _native.FLAG_F16_RANGE         # reported: this result was computed with fp32 MFMA
-            return out
-
-    def _inpaint_modules_once(self, molecule, node_mask_fixed, num_resamplings, jump_length, return_frames, num_timesteps, context, generate_x_only,
                               noise_fn, seed):
         """inpaint (:1582-1789, the two repairs of the fused method's docstring) step by step through the reference-signature methods of this class:
         torch algebra on the device around one network evaluation per step.  Serves ``generate_x_only`` (position-only diffusion: the molecule is
         its positions, z = z_x, [N, 3] out -- the dynamics network must be built without node features, as for mol_gen_sample) and configurations
-        the fused kernels are not built for.  ``noise_fn(k)``: raw draws in the reference's order; otherwise a device generator seeded with ``seed``."""
+        the fused kernels are not built for.  ``noise_fn(k)``: raw draws in the reference's order; otherwise a device generator seeded with ``seed``
+        (so that a re-run after F16RangeError draws the same noise)."""
         device = torch.device(molecule["x"].device)
         nx = self.num_x_dims
         if generate_x_only and getattr(self.dynamics_network, "num_atom_types", 0) + int(getattr(self.dynamics_network, "include_charges", False)) > 0:
@@ -1159,16 +1168,19 @@ class EquivariantVariationalDiffusion(nn.Module):
             st = ln.lib.gcdm_sample_final(ln.h, ptr(w["z"]), ptr(w["ctx"]), None, w["seed"], ptr(w["out"]), ptr(w["flags"]), C.c_void_p(ln.stream.cuda_stream))
             _native.check(ln.lib, ln.h, st, "gcdm_sample_final")
         torch.cuda.synchronize(device)
-        results = []
+        results, fl_all = [], 0
         for b, w in enumerate(work):
             fl = int(w["flags"].item())
             if fl & _native.FLAG_F16_RANGE:                    # rare: redo this batch on the primary handle (which falls back to fp32 MFMA)
                 log.warning("An activation left the f16 range in a concurrent batch; re-running it with fp32 MFMA.")
+                if fl & _native.FLAG_TAIL:
+                    self.dynamics_network.disable_fused_layer("mol_gen_sample_concurrent")
                 results.append(self.mol_gen_sample(len(num_nodes_list[b]), num_nodes_list[b], device, num_timesteps=T, context=contexts[b], seed=seeds[b]))
+                fl_all |= self.last_flags
                 continue
-            if fl & _native.FLAG_NAN_VEL:
-                log.warning("Detected NaN in `vel` -> GCPNet `vel` output was reset to zero for at least one time step.")
+            fl_all |= self._report_flags(fl, "mol_gen_sample_concurrent")
             results.append((w["out"], w["bi"], torch.ones_like(w["bi"]).bool()))
+        self.last_flags = fl_all
         return results
 
     def _lane_key(self, device: torch.device):
@@ -1312,9 +1324,8 @@ class EquivariantVariationalDiffusion(nn.Module):
     def _mol_gen_sample_lanes(self, num_samples, num_nodes, device, num_timesteps, t_norm, context, seed, K):
         device = torch.device(device)
         sb = self._SlicedBatch(self, num_nodes, device, context, seed, K)
-        guard = _RangeCheckpoints(device) if sb.dyn.mfma_mode == 1 else None
-        fell_back = False
         cs = torch.cuda.current_stream(device)
+        fl_all = []
 
         def fence():                         # the slices continue only after what the caller's stream has just done with their buffers
             ev = torch.cuda.Event()
@@ -1322,68 +1333,29 @@ class EquivariantVariationalDiffusion(nn.Module):
             for w in sb.sl:
                 w["lane"].stream.wait_event(ev)
 
-        def restart(point):
-            nonlocal fell_back
-            st0, (z0,) = point
-            sb.wait()
-            sb.bufs[sb.cur].copy_(z0)
-            _RangeCheckpoints.restore_flags(sb.flags, st0)
-            if not fell_back:
-                log.warning("An activation left the f16 range of the split-precision kernels; resuming from step %d with fp32 MFMA.", st0["s"])
-                for w in sb.sl:
-                    w["lane"].lib.gcdm_set_option(w["lane"].h, b"mfma_mode", 0)
-                fell_back = True
-                self.last_range_resume_step = st0["s"]
-            fence()
-            return st0["s"]
+        def final():
+            sb.final()
+            fl_all[:] = sb.flags.cpu().tolist()             # the one host sync of a clean run
+            fl = 0
+            for v in fl_all:
+                fl |= int(v)
+            return fl
 
+        def set_mode(mode):
+            for w in sb.sl:
+                w["lane"].lib.gcdm_set_option(w["lane"].h, b"mfma_mode", mode)
+
+        guard = _RangeCheckpoints(active=sb.dyn.mfma_mode == 1)
         try:
             sb.init()
-            s = num_timesteps - 1
-            if guard is not None:
-                sb.wait()
-                guard.good = ({"s": s}, [sb.bufs[sb.cur].clone()])
-                fence()
-            while True:
-                while s >= 0:
-                    if guard is not None and not fell_back and (num_timesteps - 1 - s) % RANGE_CHECK_EVERY == 0 and s != num_timesteps - 1:
-                        sb.wait()
-                        point = guard.snapshot({"s": s}, [sb.bufs[sb.cur]], sb.flags)
-                        fence()
-                        if point is not None:
-                            s = restart(point)
-                            continue
-                    sb.step(s, t_norm)
-                    s -= 1
-                sb.final()
-                fl_all = sb.flags.cpu().tolist()                 # the one host sync of a clean run
-                fl = 0
-                for v in fl_all:
-                    fl |= int(v)
-                point = guard.resolve(fl) if (guard is not None and not fell_back) else None
-                if point is None:
-                    break
-                s = restart(point)
+            fl = guard.run(num_timesteps, lambda s: sb.step(s, t_norm), final, sb.flags, lambda: ({}, [sb.bufs[sb.cur]]),
+                           lambda st, copies: sb.bufs[sb.cur].copy_(copies[0]), set_mode, wait=sb.wait, fence=fence)
         finally:
-            if fell_back:
-                for w in sb.sl:
-                    w["lane"].lib.gcdm_set_option(w["lane"].h, b"mfma_mode", 1)
             sb.close()
-        if fl & _native.FLAG_F16_RANGE:
-            raise RuntimeError("f16 range flag raised in fp32 mode (internal error)")
-        if fell_back:
-            fl |= _native.FLAG_F16_RANGE              # reported in last_flags: part of this sample was computed with fp32 MFMA
-        self.last_range_rewinds = 0 if guard is None else guard.rewinds
-        if not fell_back:
-            self.last_range_resume_step = None
+        self._report_flags(fl, "mol_gen_sample", guard)
         drift = [bool(int(v) & _native.FLAG_COG_DRIFT) for v in fl_all]
         if any(drift) and not all(drift):
             sb.recentre_undrifted(drift)
-        if fl & _native.FLAG_NAN_VEL:
-            log.warning("Detected NaN in `vel` -> GCPNet `vel` output was reset to zero for at least one time step.")
-        if fl & _native.FLAG_COG_DRIFT:
-            log.warning("CoG drift above 5e-2. Projected the positions down.")
-        self.last_flags = fl
         return sb.out, sb.batch_index, torch.ones_like(sb.batch_index).bool()
 
     def get_repaint_schedule(self, resamplings: int, jump_length: int, num_timesteps: int) -> List[int]:

@@ -177,9 +177,11 @@ def test_concurrent_batches_equal_sequential():
     model = model.cuda()
     lists = [torch.tensor([5, 19, 7]), torch.tensor([12, 3]), torch.tensor([19, 19, 19, 4])]
     seq = [model.ddpm.mol_gen_sample(len(nn_), nn_, "cuda", num_timesteps=6, seed=77 + b)[0].clone() for b, nn_ in enumerate(lists)]
+    model.ddpm.last_flags = -1                 # (stale value: the concurrent call reports its own)
     con = model.ddpm.mol_gen_sample_concurrent(lists, "cuda", num_timesteps=6, seeds=[77, 78, 79])
     for a, (b_, bi, _) in zip(seq, con):
         assert torch.equal(a, b_)
+    assert model.ddpm.last_flags == 0          # the OR of the batches' flag words: all clean
     torch.manual_seed(3)
     r1 = model.sample_and_analyze(num_samples=17, batch_size=5, num_timesteps=8)
     torch.manual_seed(3)
