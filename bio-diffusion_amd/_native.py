@@ -13,12 +13,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB_PATH = os.path.join(_HERE, "libgcdm_hip.so")
 LIB_PATH = os.environ.get("GCDM_HIP_LIB") or DEFAULT_LIB_PATH
 SOURCES = [os.path.join(_HERE, "csrc", "gcdm_api.hip")]
-HEADERS = ([os.path.join(_HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(_HERE, "csrc"))) if f.endswith(".h") and f != "gcdm_ops.hip.h"]
+HEADERS = ([os.path.join(_HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(_HERE, "csrc"))) if f.endswith(".h") and not f.startswith("gcdm_ops.")]
            + [os.path.join(os.path.dirname(_HERE), "include", "gcdm_hip.h")])
 # the module-level operators (forward + backward) live in their own small library (include/gcdm_ops.h)
 OPS_LIB_PATH = os.path.join(_HERE, "libgcdm_ops.so")
 OPS_SOURCES = [os.path.join(_HERE, "csrc", "gcdm_ops.hip")]
-OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_ops.h")]
+OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_ops.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.mp_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_train.h")]
 ABI_VERSION = 2
 
 FLAG_NAN_VEL, FLAG_MEAN_NOT_ZERO, FLAG_COG_DRIFT, FLAG_F16_RANGE = 1, 2, 4, 8
@@ -125,6 +126,13 @@ OPS_SIGNATURES = {
     "gcdm_op_fc_edges": [P, P, I32, P, P, I64, P],
 }
 OPS_EXPORTS = list(OPS_SIGNATURES)
+# the fused message layer for training (include/gcdm_mp_train.h), exported from the same library
+MP_TRAIN_SIGNATURES = {
+    "gcdm_mp_workspace_bytes": [I32, I64, I64, I32, I32],
+    "gcdm_mp_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, I32, I64, I64, I32, I32, P],
+    "gcdm_mp_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I32, I32, P],
+}
+MP_TRAIN_RESTYPES = {"gcdm_mp_workspace_bytes": C.c_int64}
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -136,10 +144,10 @@ def load_ops() -> C.CDLL:
     if not os.path.exists(OPS_LIB_PATH):
         raise RuntimeError(f"{OPS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
     lib = C.CDLL(OPS_LIB_PATH)
-    for name, sig in OPS_SIGNATURES.items():
+    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = sig
-        fn.restype = C.c_int
+        fn.restype = MP_TRAIN_RESTYPES.get(name, C.c_int)
     _ops_lib = lib
     return lib
 

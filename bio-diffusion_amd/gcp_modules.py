@@ -425,6 +425,50 @@ class GCPMessagePassing(nn.Module):
         self.message_fusion = nn.ModuleList(mods)
         if self.use_scalar_message_attention:
             self.scalar_message_attention = nn.Sequential(nn.Linear(output_dims[0], 1), nn.Sigmoid())
+        # Which kernels evaluate forward(): "operators" (default) = the module graph on the HIP operators, any configuration; "fused" = the
+        # whole message function as one autograd node (ops.message_layer), for the configuration why_not_fused() accepts.
+        self.path = "operators"
+
+    def why_not_fused(self) -> Optional[str]:
+        """None if ops.message_layer (include/gcdm_mp_train.h) implements this message configuration, else the first reason it does not."""
+        mods = list(self.message_fusion)
+        checks = [
+            (self.reduce_function == "sum", f"reduce_function = {self.reduce_function!r}"),
+            (self.use_scalar_message_attention, "no scalar message attention"),
+            (self.use_residual_message_gcp and len(mods) == 4, "mp_cfg: 4 residual message GCPs"),
+            (all(type(m) is GCP2 for m in mods), "module_cfg.selected_GCP is not GCP2"),
+            (all(m.vector_gate and not m.frame_gate for m in mods), "vector_gate / frame_gate"),
+            (not any(m.vector_residual for m in mods), "vector residuals"),
+            (not any(m.ablate_frame_updates or m.ablate_scalars or m.ablate_vectors for m in mods), "ablation flags"),
+            (all(tuple(str(n).lower() for n in m.nonlinearities) == ("silu", "silu") for m in mods), "nonlinearities other than silu"),
+            (all(m.bottleneck == 4 for m in mods), "bottleneck != 4"),
+            (all(not m.feedforward_out and m.sv_dim == 3 for m in mods), "feedforward_out / scalarization_vectorization_output_dim"),
+            ((self.scalar_input_dim, self.vector_input_dim) == ops.MP_NODE_DIMS and (self.scalar_output_dim, self.vector_output_dim) == ops.MP_NODE_DIMS
+             and (self.edge_scalar_dim, self.edge_vector_dim) in ops.MP_EDGE_DIMS,
+             f"hidden sizes {(self.scalar_input_dim, self.vector_input_dim)} / {(self.edge_scalar_dim, self.edge_vector_dim)}"),
+        ]
+        for ok, why in checks:
+            if not ok:
+                return why
+        return None
+
+    def set_path(self, path: str) -> None:
+        if path not in ("operators", "fused"):
+            raise ValueError(f"GCPMessagePassing.path must be 'operators' or 'fused', got {path!r}")
+        if path == "fused":
+            why = self.why_not_fused()
+            if why is not None:
+                raise NotImplementedError(f"message path 'fused': the fused message layer does not implement this configuration ({why})")
+        self.path = path
+
+    def fused_weights(self):
+        """The 30 tensors of ops.message_layer in the order of include/gcdm_mp_train.h."""
+        ws = []
+        for m in self.message_fusion:
+            ws += [m.vector_down.weight, m.vector_down_frames.weight, m.scalar_out.weight, m.scalar_out.bias, m.vector_up.weight,
+                   m.vector_out_scale.weight, m.vector_out_scale.bias]
+        lin = self.scalar_message_attention[0]
+        return ws + [lin.weight, lin.bias]
 
     def message(self, node_rep: SV, edge_rep: SV, edge_index: torch.Tensor, frames: torch.Tensor, node_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         g = ops.graph_of(edge_index, node_rep[0].shape[0])
@@ -449,6 +493,15 @@ class GCPMessagePassing(nn.Module):
         return ops.scatter_rows(message, ops.graph_of(edge_index, dim_size), self.reduce_function)
 
     def forward(self, node_rep: SV, edge_rep: SV, edge_index: torch.Tensor, frames: torch.Tensor, node_mask: Optional[torch.Tensor] = None) -> SV:
+        if self.path == "fused":
+            why = self.why_not_fused()
+            if why is not None:
+                raise NotImplementedError(f"message path 'fused': the fused message layer does not implement this configuration ({why})")
+            edge_mask = None
+            if node_mask is not None and not bool(node_mask.all()):          # as _entity_frames: an edge with a masked end point has a zero frame
+                edge_mask = node_mask[edge_index[0]] & node_mask[edge_index[1]]
+            return ops.message_layer(node_rep[0], node_rep[1], edge_rep[0], edge_rep[1], frames, ops.graph_of(edge_index, node_rep[0].shape[0]),
+                                     self.fused_weights(), edge_mask=edge_mask)
         message = self.message(node_rep, edge_rep, edge_index, frames, node_mask=node_mask)
         return sv_recover(self.aggregate(message, edge_index, dim_size=node_rep[0].shape[0]), self.vector_output_dim)
 

@@ -129,6 +129,25 @@ class GCPNetDynamics(nn.Module):
                 return why
         return None
 
+    def set_message_path(self, path: str) -> None:
+        """"operators" (default) | "fused": how the message function of every interaction layer runs on the module path (training, and any
+        forward_modules call).  "fused" = one autograd node per layer on libgcdm_ops.so's fused message kernels (include/gcdm_mp_train.h);
+        raises NotImplementedError naming the first reason when the configuration is outside what they implement."""
+        if path not in ("operators", "fused"):
+            raise ValueError(f"message path must be 'operators' or 'fused', got {path!r}")
+        if path == "fused":
+            for layer in self.interaction_layers:
+                why = layer.interaction.why_not_fused()
+                if why is not None:
+                    raise NotImplementedError(f"message path 'fused': the fused message layer does not implement this configuration ({why})")
+        for layer in self.interaction_layers:
+            layer.interaction.set_path(path)
+
+    @property
+    def message_path(self) -> str:
+        paths = {layer.interaction.path for layer in self.interaction_layers}
+        return paths.pop() if len(paths) == 1 else "mixed"
+
     def _dropout_active(self) -> bool:
         return self.training and any(l.gcp_dropout[0].use_gcp_dropout and l.gcp_dropout[0].drop_rate > 0 for l in self.interaction_layers)
 

@@ -290,6 +290,19 @@ class Graph:
             raise IndexError(f"edge_index holds a node index outside [0, {N})")
         if f & 1:
             raise ValueError("edge_index must be sorted by its first row (source node), as get_fully_connected_edge_index produces it")
+        self._col_order = None
+
+    def col_order(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(colperm, colptr): a stable argsort of col and the CSR pointers of col[colperm] -- the fixed order of every column sum of the fused
+        message layer's backward.  Computed once per graph."""
+        if self._col_order is None:
+            perm = torch.sort(self.col, stable=True).indices
+            colptr = torch.empty(self.N + 1, dtype=torch.int32, device=self.col.device)
+            flag = torch.zeros(1, dtype=torch.int32, device=self.col.device)
+            csorted = self.col[perm].contiguous()
+            _chk(_lib().gcdm_op_rowptr(_p(csorted), self.E, self.N, _p(colptr), _p(flag), _st(csorted)), "gcdm_op_rowptr")
+            self._col_order = (perm.contiguous(), colptr)
+        return self._col_order
 
 
 _GRAPH_CACHE = {}
@@ -498,3 +511,111 @@ def fully_connected_edge_index(num_nodes: torch.Tensor, device) -> torch.Tensor:
     _chk(_lib().gcdm_op_fc_edges(_p(noff_d), _p(eoff_d), len(nn_), C.c_void_p(ei.data_ptr()), C.c_void_p(ei.data_ptr() + 8 * E), E,
                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gcdm_op_fc_edges")
     return ei
+
+
+# ---- the message function of one interaction layer as one autograd node (include/gcdm_mp_train.h) -------------------------------------------
+MP_NODE_DIMS = (256, 32)
+MP_EDGE_DIMS = ((64, 16), (16, 8))
+MP_NUM_WEIGHTS = 30
+
+
+def mp_workspace_bytes(which: int, N: int, E: int, SE: int, VE: int) -> int:
+    n = int(_lib().gcdm_mp_workspace_bytes(int(which), int(N), int(E), int(SE), int(VE)))
+    if n < 0:
+        raise ValueError(f"gcdm_mp_workspace_bytes({which}, N={N}, E={E}, SE={SE}, VE={VE}): bad argument")
+    return n
+
+
+def _mp_shapes(h, chi, e, xi, frames, graph, weights):
+    N, E = graph.N, graph.E
+    _shape(len(weights) == MP_NUM_WEIGHTS, f"message_layer: {len(weights)} weight tensors, expected {MP_NUM_WEIGHTS}")
+    _shape(tuple(h.shape) == (N, MP_NODE_DIMS[0]), f"message_layer: h {tuple(h.shape)} must be [{N}, {MP_NODE_DIMS[0]}]")
+    _shape(tuple(chi.shape) == (N, MP_NODE_DIMS[1], 3), f"message_layer: chi {tuple(chi.shape)} must be [{N}, {MP_NODE_DIMS[1]}, 3]")
+    _shape(e.dim() == 2 and e.shape[0] == E and xi.dim() == 3 and tuple(xi.shape[::2]) == (E, 3) and (e.shape[1], xi.shape[1]) in MP_EDGE_DIMS,
+           f"message_layer: edge features {tuple(e.shape)} / {tuple(xi.shape)}: edge dims must be one of {MP_EDGE_DIMS} for {E} edges")
+    _shape(frames.shape[0] == E and frames.numel() == 9 * E, f"message_layer: frames {tuple(frames.shape)} for {E} edges")
+    SE, VE = int(e.shape[1]), int(xi.shape[1])
+    vin0, h0 = 2 * MP_NODE_DIMS[1] + VE, (2 * MP_NODE_DIMS[1] + VE) // 4
+    want = []
+    for k in range(4):
+        hk, vin, kin = (h0, vin0, 2 * 256 + SE + h0 + 9) if k == 0 else (8, 32, 256 + 8 + 9)
+        want += [(hk, vin), (3, vin), (256, kin), (256,), (32, hk), (32, 256), (32,)]
+    want += [(1, 256), (1,)]
+    for i, (w, s) in enumerate(zip(weights, want)):
+        _shape(tuple(w.shape) == s, f"message_layer: weight {i} has shape {tuple(w.shape)}, expected {s}")
+    for t in (h, chi, e, xi, frames, *weights):
+        if t.dtype != torch.float32:
+            raise TypeError(f"message_layer: the fused message layer computes in fp32; got a {t.dtype} tensor")
+        _dev(t)
+    return SE, VE
+
+
+class _MessageLayer(torch.autograd.Function):
+    """GCPMessagePassing.forward of the production message configuration: two C calls (gcdm_mp_fwd / gcdm_mp_bwd).  The tape -- what the
+    backward reads -- is one workspace tensor held by the context and dropped by the backward; under no_grad the forward writes none."""
+
+    @staticmethod
+    def forward(ctx, h, chi, e, xi, frames, graph, edge_mask, record, *weights):
+        SE, VE = _mp_shapes(h, chi, e, xi, frames, graph, weights)
+        N, E = graph.N, graph.E
+        hs, cs, es, xs = h.detach().contiguous(), chi.detach().contiguous(), e.detach().contiguous(), xi.detach().contiguous()
+        fs = frames.detach().reshape(E, 9).contiguous()
+        ws = [w.detach().contiguous() for w in weights]
+        mk = None if edge_mask is None else edge_mask.reshape(-1).to(torch.uint8).contiguous()
+        _shape(mk is None or mk.numel() == E, "message_layer: edge_mask must have one entry per edge")
+        alloc = torch.zeros if E == 0 else torch.empty          # no edges: the library writes nothing, the sums are zero
+        agg = alloc((N, 256 + 3 * 32), dtype=torch.float32, device=h.device)
+        tape = bool(record)                 # (grad mode is off inside forward: the caller says whether a graph is being recorded)
+        ws_t = torch.empty(mp_workspace_bytes(int(tape), N, E, SE, VE) // 4, dtype=torch.float32, device=h.device)
+        wp = (C.c_void_p * MP_NUM_WEIGHTS)(*[w.data_ptr() for w in ws])
+        _chk(_lib().gcdm_mp_fwd(_p(hs), _p(cs), _p(es), _p(xs), _p(graph.row), _p(graph.col), _p(graph.rowptr), _p(fs), _p(mk), wp, _p(agg), _p(ws_t),
+                                int(tape), N, E, SE, VE, _st(hs)), "gcdm_mp_fwd")
+        ctx.tape = ws_t if tape else None
+        del ws_t
+        ctx.graph, ctx.frames, ctx.mask, ctx.dims = graph, fs, mk, (N, E, SE, VE)
+        ctx.save_for_backward(hs, *weights)
+        ctx.ws = ws
+        return agg
+
+    @staticmethod
+    def backward(ctx, dagg):
+        if torch.is_grad_enabled():
+            raise RuntimeError("message_layer (fused message path): double backward (create_graph=True) is not supported; use the operator path")
+        if ctx.tape is None:
+            raise RuntimeError("message_layer: the tape of this forward is gone (a second backward through the same graph is not supported)")
+        saved = ctx.saved_tensors
+        hs = saved[0]
+        N, E, SE, VE = ctx.dims
+        g = _f(dagg).reshape(N, 256 + 3 * 32)
+        dev = g.device
+        colperm, colptr = ctx.graph.col_order()
+        alloc = torch.zeros if E == 0 else torch.empty
+        dh = alloc((N, 256), dtype=torch.float32, device=dev)
+        dchi = alloc((N, 32, 3), dtype=torch.float32, device=dev)
+        de = alloc((E, SE), dtype=torch.float32, device=dev)
+        dxi = alloc((E, VE, 3), dtype=torch.float32, device=dev)
+        dw = alloc(mp_workspace_bytes(3, N, E, SE, VE) // 4, dtype=torch.float32, device=dev)
+        scratch = torch.empty(mp_workspace_bytes(2, N, E, SE, VE) // 4, dtype=torch.float32, device=dev)
+        wp = (C.c_void_p * MP_NUM_WEIGHTS)(*[w.data_ptr() for w in ctx.ws])
+        _chk(_lib().gcdm_mp_bwd(_p(g), _p(hs), _p(ctx.graph.row), _p(ctx.graph.col), _p(ctx.graph.rowptr), _p(colptr), _p(colperm), _p(ctx.frames),
+                                _p(ctx.mask), wp, _p(ctx.tape), _p(scratch), _p(dh), _p(dchi), _p(de), _p(dxi), _p(dw), N, E, SE, VE, _st(g)), "gcdm_mp_bwd")
+        ctx.tape = None
+        del scratch
+        grads, o = [], 0
+        for w in ctx.ws:
+            grads.append(dw[o: o + w.numel()].view(w.shape))
+            o += w.numel()
+        ctx.ws = None
+        need = ctx.needs_input_grad
+        return ((dh if need[0] else None), (dchi if need[1] else None), (de if need[2] else None), (dxi if need[3] else None), None, None, None, None,
+                *[gr if need[8 + i] else None for i, gr in enumerate(grads)])
+
+
+def message_layer(h: torch.Tensor, chi: torch.Tensor, e: torch.Tensor, xi: torch.Tensor, frames: torch.Tensor, graph: Graph, weights,
+                  edge_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The message function + sum aggregation of one interaction layer (GCPMessagePassing.forward, production configuration) as one autograd
+    node on libgcdm_ops.so's fused kernels.  ``weights``: the 30 tensors in the order of include/gcdm_mp_train.h.  -> (agg_s [N, 256],
+    agg_v [N, 32, 3]).  Raises (no fallback) for shapes, dims or dtypes the kernels do not take; the edge list must be row-sorted (``graph``)."""
+    record = torch.is_grad_enabled() and any(t.requires_grad for t in (h, chi, e, xi, *weights))
+    agg = _MessageLayer.apply(h, chi, e, xi, frames, graph, edge_mask, record, *weights)
+    return agg[:, :256], agg[:, 256:].reshape(graph.N, 32, 3)

@@ -1,7 +1,10 @@
 """Where a training step of the module path spends its time (GPU box): wall clock per step against the GPU-side kernel time of the same steps.
 
-    python tools/train_step_probe.py [steps]                       -> wall ms / step, HIP-event ms / step, launches per step (torch profiler-free: counted by rocprofv3)
+    python tools/train_step_probe.py [steps] [--message-path operators|fused]   -> wall ms / step, host enqueue ms / step, HIP-event ms / step
     rocprofv3 --kernel-trace --stats -- python tools/train_step_probe.py 5      (sum of kernel durations / steps = GPU busy time per step)
+
+--message-path fused runs every interaction layer's message function as one autograd node on the fused message kernels
+(GCPNetDynamics.set_message_path, include/gcdm_mp_train.h); the default is the operator path bench.py times.
 
 The step is bench.py's `training_step`: forward in training mode + loss + backward of one 64-molecule QM9 batch through libgcdm_ops.so's operators."""
 import importlib
@@ -15,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 
-def build_step():
+def build_step(message_path="operators"):
     import synth
     pkg = importlib.import_module("bio-diffusion_amd")
     dev = torch.device("cuda", 0)
@@ -28,6 +31,7 @@ def build_step():
             if p.dim() == 2:
                 p.mul_(0.25)
     net = net.to(dev)
+    net.set_message_path(message_path)
     info = pkg.dataset_info("qm9")
     ddpm = pkg.EquivariantVariationalDiffusion(net, cfgs["diffusion_cfg"], cfgs["dataloader_cfg"], info).to(dev)
     ddpm._native(dev)
@@ -53,8 +57,13 @@ def build_step():
 
 
 def main():
-    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-    once, dev = build_step()
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("steps", nargs="?", type=int, default=10)
+    ap.add_argument("--message-path", choices=("operators", "fused"), default="operators")
+    args = ap.parse_args()
+    steps = args.steps
+    once, dev = build_step(args.message_path)
     for _ in range(3):
         once()
     torch.cuda.synchronize(dev)
@@ -67,7 +76,7 @@ def main():
     t_host = (time.perf_counter() - t0) / steps * 1e3          # host done enqueueing
     torch.cuda.synchronize(dev)
     wall = (time.perf_counter() - t0) / steps * 1e3
-    print(f"training step, 64 x 19: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
+    print(f"training step, 64 x 19, message path {args.message_path}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
 
 
 if __name__ == "__main__":
