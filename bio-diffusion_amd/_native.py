@@ -19,7 +19,8 @@ HEADERS = ([os.path.join(_HERE, "csrc", f) for f in sorted(os.listdir(os.path.jo
 OPS_LIB_PATH = os.path.join(_HERE, "libgcdm_ops.so")
 OPS_SOURCES = [os.path.join(_HERE, "csrc", "gcdm_ops.hip")]
 OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_ops.h"),
-               os.path.join(_HERE, "csrc", "gcdm_ops.mp_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_train.h")]
+               os.path.join(_HERE, "csrc", "gcdm_ops.mp_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_train.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h")]
 ABI_VERSION = 2
 
 FLAG_NAN_VEL, FLAG_MEAN_NOT_ZERO, FLAG_COG_DRIFT, FLAG_F16_RANGE = 1, 2, 4, 8
@@ -133,6 +134,16 @@ MP_TRAIN_SIGNATURES = {
     "gcdm_mp_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I32, I32, P],
 }
 MP_TRAIN_RESTYPES = {"gcdm_mp_workspace_bytes": C.c_int64}
+# the fused training update: clipping, AdamW / AMSGrad, EMA (include/gcdm_optim.h), exported from the same library
+D = C.c_double
+OPTIM_SIGNATURES = {
+    "gcdm_optim_workspace_bytes": [I32, I64, I64, I32],
+    "gcdm_optim_step": [P, P, I64, I64, I64, D, D, D, D, D, I32, I32, I32, I32, D, I64, I64, P],
+    "gcdm_optim_ema_swap": [P, P, I64, I64, I64, I32, I32, P],
+}
+OPTIM_RESTYPES = {"gcdm_optim_workspace_bytes": C.c_int64}
+OPTIM_QUEUE_MAX = 1024          # GCDM_OPTIM_QUEUE_MAX
+OPTIM_FLAG_NONFINITE = 1        # GCDM_OPTIM_FLAG_NONFINITE
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -144,10 +155,10 @@ def load_ops() -> C.CDLL:
     if not os.path.exists(OPS_LIB_PATH):
         raise RuntimeError(f"{OPS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
     lib = C.CDLL(OPS_LIB_PATH)
-    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()):
+    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = sig
-        fn.restype = MP_TRAIN_RESTYPES.get(name, C.c_int)
+        fn.restype = {**MP_TRAIN_RESTYPES, **OPTIM_RESTYPES}.get(name, C.c_int)
     _ops_lib = lib
     return lib
 

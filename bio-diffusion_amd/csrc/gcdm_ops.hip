@@ -1,8 +1,10 @@
 // libgcdm_ops.so -- the module-level operators (forward + backward) behind plug point 3, the non-production configurations and the
-// training objective, and the fused message layer for training.  One translation unit, independent of libgcdm_hip.so (the fused sampling
-// path); C ABI in include/gcdm_ops.h and include/gcdm_mp_train.h.
+// training objective, the fused message layer for training, and the fused training update.  One translation unit, independent of libgcdm_hip.so (the fused sampling
+// path); C ABI in include/gcdm_ops.h, include/gcdm_mp_train.h and include/gcdm_optim.h.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -o bio-diffusion_amd/libgcdm_ops.so bio-diffusion_amd/csrc/gcdm_ops.hip
 #include "gcdm_ops.hip.h"
 #include "../../include/gcdm_ops.h"
 #include "gcdm_ops.mp_train.hip.h"
 #include "../../include/gcdm_mp_train.h"
+#include "../../include/gcdm_optim.h"
+#include "gcdm_ops.optim.hip.h"

@@ -204,6 +204,16 @@ class _MoleculeGenerationDDPM(nn.Module):
     def step(self, batch: Any, **kw) -> Tuple[torch.Tensor, Dict[str, Any]]:
         return self.forward(batch, **kw)
 
+    def configure_optimizers(self):
+        """The reference's update after backward() as one fused step (optim.TrainingUpdate): AdamW(lr=1e-4, weight_decay=1e-12,
+        amsgrad=True) of configs/model/*_mol_gen_ddpm.yaml, the adaptive clipping of configure_gradient_clipping when
+        ``module_cfg.clip_gradients``, and the EMA of configs/callbacks/ema.yaml (decay 0.9999 every step from step 0).  Move the module to
+        the GPU first."""
+        from .optim import TrainingUpdate
+        clip = bool(cfg_get(self._init_kwargs["module_cfg"], "clip_gradients", True))
+        return TrainingUpdate(self.parameters(), lr=1e-4, weight_decay=1e-12, amsgrad=True, clip_gradients=clip, queue_len=50,
+                              ema_decay=0.9999, ema_every=1, ema_start=0)
+
     @torch.inference_mode()
     def validation_step(self, batch: Any, batch_idx: int = 0, **kw) -> Dict[str, Any]:
         """The metrics dictionary of the reference's validation / test step (without the Lightning logging around it)."""

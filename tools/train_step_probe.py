@@ -3,6 +3,9 @@
     python tools/train_step_probe.py [steps] [--message-path operators|fused]   -> wall ms / step, host enqueue ms / step, HIP-event ms / step
     rocprofv3 --kernel-trace --stats -- python tools/train_step_probe.py 5      (sum of kernel durations / steps = GPU busy time per step)
 
+--update torch|fused adds the update after backward(): `torch` the reference's recipe in stock torch (adaptive clipping with two host
+syncs, AdamW amsgrad, the per-entry EMA), `fused` optim.TrainingUpdate (three launches); the default `none` is the bare forward + backward.
+
 --message-path fused runs every interaction layer's message function as one autograd node on the fused message kernels
 (GCPNetDynamics.set_message_path, include/gcdm_mp_train.h); the default is the operator path bench.py times.
 
@@ -18,7 +21,30 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 
-def build_step(message_path="operators"):
+def _torch_update(params):
+    """The reference's recipe in stock torch: adaptive clipping (Queue + get_grad_norm + clip_grad_norm_), AdamW(amsgrad), per-entry EMA."""
+    import numpy as np
+    opt = torch.optim.AdamW(params, lr=1e-4, weight_decay=1e-12, amsgrad=True)
+    ema = [p.detach().clone() for p in params]
+    queue = [3000.0]
+
+    def step():
+        ps = [p for p in params if p.grad is not None]
+        max_norm = 1.5 * np.mean(queue) + 2 * np.std(queue)
+        norm = torch.norm(torch.stack([torch.norm(p.grad.detach(), 2.0) for p in ps]), 2.0)
+        torch.nn.utils.clip_grad_norm_(ps, max_norm)
+        queue.insert(0, float(max_norm) if float(norm) > max_norm else float(norm))
+        del queue[50:]
+        opt.step()
+        with torch.no_grad():
+            for e, p in zip(ema, params):
+                diff = e - p
+                diff.mul_(1.0 - 0.9999)
+                e.sub_(diff)
+    return step
+
+
+def build_step(message_path="operators", update="none"):
     import synth
     pkg = importlib.import_module("bio-diffusion_amd")
     dev = torch.device("cuda", 0)
@@ -47,11 +73,20 @@ def build_step(message_path="operators"):
                              num_graphs=Bt, num_nodes_present=nt_)
     ddpm.train()
 
+    params = list(ddpm.parameters())
+    upd = None
+    if update == "torch":
+        upd = _torch_update(params)
+    elif update == "fused":
+        upd = pkg.TrainingUpdate(params).step
+
     def once():
-        for p_ in ddpm.parameters():
+        for p_ in params:
             p_.grad = None
         terms = ddpm(tb)
         (terms[1] + terms[3] + terms[4]).mean().backward()
+        if upd is not None:
+            upd()
 
     return once, dev
 
@@ -61,9 +96,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("steps", nargs="?", type=int, default=10)
     ap.add_argument("--message-path", choices=("operators", "fused"), default="operators")
+    ap.add_argument("--update", choices=("none", "torch", "fused"), default="none")
     args = ap.parse_args()
     steps = args.steps
-    once, dev = build_step(args.message_path)
+    once, dev = build_step(args.message_path, args.update)
     for _ in range(3):
         once()
     torch.cuda.synchronize(dev)
@@ -76,7 +112,7 @@ def main():
     t_host = (time.perf_counter() - t0) / steps * 1e3          # host done enqueueing
     torch.cuda.synchronize(dev)
     wall = (time.perf_counter() - t0) / steps * 1e3
-    print(f"training step, 64 x 19, message path {args.message_path}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
+    print(f"training step, 64 x 19, message path {args.message_path}, update {args.update}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
 
 
 if __name__ == "__main__":
