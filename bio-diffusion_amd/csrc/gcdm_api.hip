@@ -5,9 +5,6 @@
 #include "gcdm_node_x3.hip.h"
 #include "gcdm_node_x3w.hip.h"
 #include "gcdm_layer_x3.hip.h"
-#ifndef GCDM_FUSE_TILE_DEFAULT
-#define GCDM_FUSE_TILE_DEFAULT 32
-#endif
 #include "gcdm_embed_x3.hip.h"
 #include "gcdm_stability.hip.h"
 #include "../../include/gcdm_hip.h"
@@ -77,13 +74,12 @@ struct gcdm_handle {
           *VDI = nullptr, *VDJ = nullptr, *AGG = nullptr, *PART = nullptr, *VEL = nullptr, *EPS = nullptr, *EP4 = nullptr, *AL = nullptr, *U = nullptr, *FR = nullptr, *PROF = nullptr, *ZK = nullptr, *ZU = nullptr, *ZROW = nullptr;
     float *PQ4b = nullptr, *VDIb = nullptr, *VDJb = nullptr;   // second set of the node-level msg0 halves: layer l gathers set l & 1, its node tiles write set (l + 1) & 1 (round 6:
                                                                // with the node tiles as a tail role of the edge workgroups both happen in ONE launch)
-    // Fused layer launch (gcdm_layer_x3.hip.h): tables of the node-tile queue for 32- and 64-node tiles ([0] / [1]); null when the plan does not qualify
-    int* d_tail_tab[2] = {nullptr, nullptr};       // qstart[9] | rel_node_end[8] | need[node tiles]
-    int* d_tail_ctr = nullptr;                     // ready[node tiles of 32] | qcur[17]  (zeroed at plan time, self-resetting)
+    // Fused layer launch (gcdm_layer_x3.hip.h): table of the node-tile queue (TailArgs::tab; null when the plan does not qualify) and its counters
+    int* d_tail_tab = nullptr;                     // per XCD [8 x + 0..3]: first owned node tile, owned node tiles, (unused), rel_node_end | [64 + t]: need[node tile t]
+    int* d_tail_ctr = nullptr;                     // ready[node tiles of 32] | qcur[TAIL_CTR_WORDS]  (zeroed at plan time, self-resetting)
     int tail_tiles32 = 0;
     int fuse_node = 1;               // option "fuse_node" / env GCDM_FUSE_NODE: 1 = the layer's node tiles run as a tail role of the persistent edge workgroups (one launch
                                      // per layer) where the plan qualifies; 0 = two launches per layer (rounds 1-5)
-    int fuse_tile = 0;               // option "fuse_tile": nodes per node tile of the tail role (32 / 64; 0 = automatic)
     int fuse_active = 0;             // option "fuse_active" (read-only): the last forward used the fused launch
     uint32_t* d_flags = nullptr;
     float* d_gmean = nullptr;
@@ -495,7 +491,8 @@ void free_plan(gcdm_handle* h) {
     if (h->d_rowstart) (void)hipFree(h->d_rowstart);
     if (h->d_mask) (void)hipFree(h->d_mask);
     h->d_mask = nullptr;
-    for (int i = 0; i < 2; ++i) { if (h->d_tail_tab[i]) (void)hipFree(h->d_tail_tab[i]); h->d_tail_tab[i] = nullptr; }
+    if (h->d_tail_tab) (void)hipFree(h->d_tail_tab);
+    h->d_tail_tab = nullptr;
     if (h->d_tail_ctr) (void)hipFree(h->d_tail_ctr);
     h->d_tail_ctr = nullptr;
     if (h->ws) (void)hipFree(h->ws);
@@ -548,7 +545,6 @@ int gcdm_create(const GcdmConfig* cfg, gcdm_handle** out) {
     if (const char* nt = getenv("GCDM_NODE_TILE")) h->node_tile = atoi(nt) == 32 ? 32 : atoi(nt) == 64 ? 64 : 0;
     if (const char* sg = getenv("GCDM_STEP_GRAPH")) h->step_graph = atoi(sg) ? 1 : 0;
     if (const char* fz = getenv("GCDM_FUSE_NODE")) h->fuse_node = atoi(fz) ? 1 : 0;
-    if (const char* fz = getenv("GCDM_FUSE_TILE")) { const int v = atoi(fz); if (v == 32) h->fuse_tile = v; }
     DeviceGuard guard(cfg->device);
     {
         int n = 0;
@@ -968,7 +964,7 @@ int gcdm_plan_batch_masked(gcdm_handle* h, int32_t B, const int32_t* nn, const u
     h->B = B; h->N = N; h->E = E; h->max_n = max_n;
     // ---- node-tile queues of the fused layer launch (gcdm_layer_x3.hip.h): 64-edge tiles, XCD x owns the x-th contiguous eighth of the tile list (the partition of
     // k_edge_msg_x3's persistent loop); node tile t (T nodes) waits for the edge tiles first_tile(t) .. last_tile(t) of its rows and is owned by the XCD whose range
-    // contains first_tile(t).  Built for T = 32 and T = 64; a plan qualifies when nothing is masked, the launch is persistent and no node tile spans three XCDs.
+    // contains first_tile(t).  A plan qualifies when nothing is masked, the launch is persistent and no node tile spans three XCDs.
     h->tail_tiles32 = 0;
     const int wgs_ = h->cus / 8 * 8;
     if (!node_mask && E > (int64_t)64 * wgs_ && wgs_ >= 8) {
@@ -976,31 +972,31 @@ int gcdm_plan_batch_masked(gcdm_handle* h, int32_t B, const int32_t* nn, const u
         int xs[9];
         for (int x = 0; x <= 8; ++x) xs[x] = x * base + std::min(x, rem);
         auto xcd_of_tile = [&](int g) { int x = 0; while (x < 7 && g >= xs[x + 1]) ++x; return x; };
-        for (int which = 0; which < 1; ++which) {          // (T = 32; the builder is generic in T)
-            const int T = which ? 64 : 32, NTt = (N + T - 1) / T;
-            std::vector<int> tab(64 + (size_t)NTt, 0);
-            std::vector<std::vector<std::pair<int, int>>> owned(8);          // per XCD: (edge tile the node item stands behind, node tile)
-            bool ok = true;
-            for (int t = 0; t < NTt && ok; ++t) {
-                const int nf = t * T, nl = std::min(nf + T, N) - 1;
-                const int ft = rowstart[nf] >> 6, lt = (rowstart[nl] + ncnt[nl] - 1) >> 6;
-                const int owner = xcd_of_tile(ft), xl = xcd_of_tile(lt);
-                if (xl > owner + 1 || lt - ft + 1 > 0xffff) ok = false;
-                tab[64 + t] = (lt - ft + 1) | ((xl != owner ? 1 : 0) << 16);
-                owned[owner].push_back({lt, t});
+        constexpr int T = 32;                              // nodes per node tile of the tail role (NodeTailRole<32>)
+        const int NTt = (N + T - 1) / T;
+        std::vector<int> tab(64 + (size_t)NTt, 0);
+        std::vector<std::vector<std::pair<int, int>>> owned(8);          // per XCD: (edge tile the node item stands behind, node tile)
+        bool ok = true;
+        for (int t = 0; t < NTt && ok; ++t) {
+            const int nf = t * T, nl = std::min(nf + T, N) - 1;
+            const int ft = rowstart[nf] >> 6, lt = (rowstart[nl] + ncnt[nl] - 1) >> 6;
+            const int owner = xcd_of_tile(ft), xl = xcd_of_tile(lt);
+            if (xl > owner + 1 || lt - ft + 1 > 0xffff) ok = false;
+            tab[64 + t] = (lt - ft + 1) | ((xl != owner ? 1 : 0) << 16);
+            owned[owner].push_back({lt, t});
+        }
+        for (int x = 0; x < 8 && ok; ++x) {
+            tab[8 * x] = owned[x].empty() ? 0 : owned[x][0].second;
+            tab[8 * x + 1] = (int)owned[x].size();
+            tab[8 * x + 2] = xs[x + 1] - xs[x] + (int)owned[x].size();
+            if (x >= 1) {                                                // rows of XCD x's first tiles that belong to the boundary node tile owned by XCD x - 1
+                const int tb = erow[(size_t)xs[x] * 64] / T;
+                if ((rowstart[tb * T] >> 6) < xs[x]) tab[8 * x + 3] = std::min((tb + 1) * T, N);
             }
-            for (int x = 0; x < 8 && ok; ++x) {
-                tab[8 * x] = owned[x].empty() ? 0 : owned[x][0].second;
-                tab[8 * x + 1] = (int)owned[x].size();
-                tab[8 * x + 2] = xs[x + 1] - xs[x] + (int)owned[x].size();
-                if (x >= 1) {                                                // rows of XCD x's first tiles that belong to the boundary node tile owned by XCD x - 1
-                    const int tb = erow[(size_t)xs[x] * 64] / T;
-                    if ((rowstart[tb * T] >> 6) < xs[x]) tab[8 * x + 3] = std::min((tb + 1) * T, N);
-                }
-            }
-            if (!ok) continue;
-            HIP_OK(h, hipMalloc(&h->d_tail_tab[which], tab.size() * sizeof(int)));
-            HIP_OK(h, hipMemcpy(h->d_tail_tab[which], tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
+        if (ok) {
+            HIP_OK(h, hipMalloc(&h->d_tail_tab, tab.size() * sizeof(int)));
+            HIP_OK(h, hipMemcpy(h->d_tail_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
         }
         h->tail_tiles32 = (N + 31) / 32;
         HIP_OK(h, hipMalloc(&h->d_tail_ctr, ((size_t)h->tail_tiles32 + TAIL_CTR_WORDS) * sizeof(int)));
@@ -1187,19 +1183,15 @@ static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, con
             bool persistent = true;
             if (h->persistent == 0 || tiles <= wgs || wgs < 8) { wgs = tiles; xa.wg_stride = tiles; persistent = false; } else xa.wg_stride = wgs / 8;
             // one launch per layer: the node tiles as a tail role of the persistent workgroups (gcdm_layer_x3.hip.h) where the plan qualifies
-            int ft = 0;
-            if (ET == 64 && persistent && h->fuse_node && !h->profile_node && !h->d_mask && h->d_tail_ctr) {
-                // nodes per node tile of the tail role: 32.  (64-node tiles -- node_tile_x3w -- were built and measured too: QM9 6.85 against 6.94 ms per step on one box,
-                // 7.30 against 7.24 on another, GEOM 3.81 against 3.75; their node code keeps one SGPR spilled, which costs the edge role a VGPR: not instantiated)
-                ft = h->d_tail_tab[0] ? 32 : 0;
-            }
-            h->fuse_active = ft != 0;
-            if (ft) {
+            // nodes per node tile of the tail role: 32.  (64-node tiles -- node_tile_x3w -- were built and measured too: QM9 6.85 against 6.94 ms per step on one box,
+            // 7.30 against 7.24 on another, GEOM 3.81 against 3.75; their node code keeps one SGPR spilled, which costs the edge role a VGPR: not instantiated)
+            h->fuse_active = ET == 64 && persistent && h->fuse_node && !h->profile_node && !h->d_mask && h->d_tail_ctr && h->d_tail_tab;
+            if (h->fuse_active) {
                 na.ff = d.ff; na.pos = d.pos;
                 set_next(l + 1);
                 if (!prep_node_x3(l + 1, &d)) return -1;
                 TailArgs ta{};
-                ta.nx = nx; ta.ready = h->d_tail_ctr; ta.qcur = h->d_tail_ctr + h->tail_tiles32; ta.tab = h->d_tail_tab[ft == 64 ? 1 : 0];
+                ta.nx = nx; ta.ready = h->d_tail_ctr; ta.qcur = h->d_tail_ctr + h->tail_tiles32; ta.tab = h->d_tail_tab;
                 ta.num_wgs = wgs;
                 {
                     NodeTailRole<32>::Args la{xa, ta};
@@ -1536,7 +1528,6 @@ int gcdm_set_option(gcdm_handle* h, const char* name, int32_t value) {
     if (k == "node_base") { if (value < 0) return fail(h, "gcdm_set_option(node_base): >= 0"); h->node_base = (uint32_t)value; return 0; }
     if (k == "persistent") { h->persistent = value ? 1 : 0; return 0; }
     if (k == "fuse_node") { h->fuse_node = value ? 1 : 0; return 0; }
-    if (k == "fuse_tile") { if (value != 0 && value != 32) return fail(h, "gcdm_set_option(fuse_tile): 0 or 32"); h->fuse_tile = value; return 0; }
     if (k == "node_tile") {
         if (value != 0 && value != 32 && value != 64) return fail(h, "gcdm_set_option: node_tile must be 0 (automatic), 32 or 64");
         h->node_tile = value;
@@ -1564,7 +1555,6 @@ int gcdm_get_option(const gcdm_handle* h, const char* name) {
     if (k == "persistent") return h->persistent;
     if (k == "fuse_node") return h->fuse_node;
     if (k == "fuse_active") return h->fuse_active;
-    if (k == "fuse_tile") return h->fuse_tile;
     if (k == "node_tile") return h->node_tile;
     if (k == "step_graph") return (h->step_graph && !h->step_graph_failed) ? 1 : 0;
     if (k == "graph_launches") return (int)(h->graph_launches & 0x7fffffff);

@@ -22,32 +22,7 @@
 // SiLU in the scaled units of this kernel: the message scalars are kept as c * m.s with c = -log2(e) (the host folds c into the weights, gcdm_api.hip
 // X3_C), so for x' = c * x:  c * SiLU(x) = x' / (1 + exp2(x'))  -- exp2, add, rcp, mul: one multiply less than x * sigmoid(x)
 #define X3_C (-1.4426950408889634f)
-// Timing ablations (-DGCDM_ABL_<piece> removes one piece of the kernel: wrong results by construction; tools/ab_run.sh reads the in-kernel end-of-tile
-// stamp of such builds, profiles/r03_ablation_edge_kernel.md is the record).  They exist only in a build that ALSO says -DGCDM_ABLATIONS.
-#ifndef GCDM_ABLATIONS
-#undef GCDM_ABL_NOSILU
-#undef GCDM_ABL_NOWLOAD
-#undef GCDM_ABL_NOB
-#undef GCDM_ABL_MFMA1
-#undef GCDM_ABL_NOGATHER
-#undef GCDM_ABL_NOCONST
-#undef GCDM_ABL_FINW
-#undef GCDM_ABL_NOP1
-#undef GCDM_ABL_NOBETA
-#undef GCDM_ABL_NOP1W
-#undef GCDM_ABL_NOPQ
-#undef GCDM_ABL_NOGATE
-#undef GCDM_ABL_GATE_NOPG
-#undef GCDM_ABL_NOSTORE
-#undef GCDM_ABL_NOAGG
-#undef GCDM_ABL_VECFMA
-#undef GCDM_ABL_VECNONE
-#endif
-#ifdef GCDM_ABL_NOSILU
-__device__ __forceinline__ float silu_scaled(float xs) { return xs; }
-#else
 __device__ __forceinline__ float silu_scaled(float xs) { return xs * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(xs)); }
-#endif
 
 // ---- packed fp32 (round 5: measured, NOT the default) -------------------------------------------------------------------------------
 // v_pk_{mul,add,fma}_f32 process an aligned register PAIR per instruction.  Every element-wise step of the VALU phases whose operands sit in
@@ -80,16 +55,12 @@ template <bool PK = X3_PK> __device__ __forceinline__ f32x2 pk_fma1(f32x2 a, flo
     else return (f32x2){__builtin_fmaf(a[0], s, c[0]), __builtin_fmaf(a[1], s, c[1])};
 }
 // SiLU (scaled units, see silu_scaled) of two adjacent channels: exp2 x2, packed add, rcp x2, packed multiply -- 6 issue slots instead of 8
-#ifdef GCDM_ABL_NOSILU
-template <bool PK = X3_PK> __device__ __forceinline__ f32x2 silu_scaled2(f32x2 xs) { return xs; }
-#else
 template <bool PK = X3_PK> __device__ __forceinline__ f32x2 silu_scaled2(f32x2 xs) {
     const f32x2 e = {__builtin_amdgcn_exp2f(xs[0]), __builtin_amdgcn_exp2f(xs[1])};
     const f32x2 d = pk_add1<PK>(e, 1.0f);
     const f32x2 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
     return pk_mul<PK>(xs, r);
 }
-#endif
 // merge of the two accumulators + SiLU over one 32 x 32 accumulator tile (16 registers per lane)
 template <bool PK = X3_PK> __device__ __forceinline__ void silu_merge16(f32x16& dst, const f32x16& am, const f32x16& al, float inv) {
 #pragma unroll
@@ -303,27 +274,17 @@ __device__ __forceinline__ void x3_prefetch_b(X3Ring<MT, PD>& ring, const WPool&
 #define X3_TAIL_BLOCKS 4
 // K' of msg0's per-edge part (kernel and host packing, gcdm_api.hip): [e' (Se) | norms of the H0 hidden vectors | 9 frame scalars | 0 ...] in units of
 // 16-deep k-blocks.  Round 5: the three pieces are COMPACT -- 64 + 20 + 9 = 93 slots = 6 k-blocks at QM9, 16 + 18 + 9 = 43 = 3 at GEOM; rounds 1-4 started
-// the norms and the frame scalars on 8-slot groups of their own (7 / 4 k-blocks; -DGCDM_X3_MSG0_PADDED brings that layout back for an A/B).  The contraction
-// order of msg0 changes with the layout: not the same bits as round 4, same error model.
-#ifdef GCDM_X3_MSG0_PADDED
-__host__ __device__ constexpr int x3_msg0_qpos(int Se, int H0) { return 8 * (Se / 8 + (H0 + 7) / 8); }
-__host__ __device__ constexpr int x3_msg0_kb(int Se, int H0) { return (x3_msg0_qpos(Se, H0) + 16 + 15) / 16; }
-#else
+// the norms and the frame scalars on 8-slot groups of their own (7 / 4 k-blocks).  The contraction order of msg0 changed with the layout: not the same bits
+// as round 4, same error model.
 __host__ __device__ constexpr int x3_msg0_qpos(int Se, int H0) { return Se + H0; }
 __host__ __device__ constexpr int x3_msg0_kb(int Se, int H0) { return (Se + H0 + 9 + 15) / 16; }
-#endif
 constexpr int X3_PD = 2;         // k-blocks of weight prefetch distance in the edge kernel (register ring of PD + 1 sets)
 #ifndef GCDM_STAMP_K
 #define GCDM_STAMP_K 0              // which residual GCP2 (0..2) carries the per-phase stamps 10..17 of a -DGCDM_STAMPS build
 #endif
-#ifndef GCDM_X3_TAIL_PER_MFMA
-#define GCDM_X3_TAIL_PER_MFMA 8      // round 5, shipped-style builds (end-of-tile stamp): 4 / 6 / 8 / 10 / 12 / 14 / 20 -> 59 360 / 59 550 / 59 460 / 59 470 / 59 670 / 59 820 / 59 530 cycles (QM9), same order at GEOM
-#endif
-#ifndef GCDM_X3_VEC_PER_MFMA
-#define GCDM_X3_VEC_PER_MFMA 6
-#endif
-constexpr int X3_TAIL_PER_MFMA = GCDM_X3_TAIL_PER_MFMA;  // tail skew: instructions of N-tile 0's SiLU issued behind each of N-tile 1's last MFMAs
-constexpr int X3_VEC_PER_MFMA = GCDM_X3_VEC_PER_MFMA;   // instructions of a vector stage issued behind each MFMA of the hosting k-block (0 / 3 / 4 / 10: +-0.3 %)
+// (both swept in round 5, 4 .. 20 and 4 .. 12: no value better beyond box noise; profiles/r05_ab_log.txt runs 17 and 18)
+constexpr int X3_TAIL_PER_MFMA = 8;      // tail skew: instructions of N-tile 0's SiLU issued behind each of N-tile 1's last MFMAs
+constexpr int X3_VEC_PER_MFMA = 6;       // instructions of a vector stage issued behind each MFMA of the hosting k-block
 
 template <int MT, int PD>
 __device__ __forceinline__ void x3_prefetch(X3Ring<MT, PD>& ring, const h8* __restrict__ wH, const h8* __restrict__ wL, int KB, int lane) {
@@ -398,6 +359,39 @@ struct NoTail {
     __device__ __forceinline__ void operator()() const {}
 };
 
+// The six products of one k-block of a tile GEMM: a wave holds two 32 x 32 output tiles t = 0, 1 (the N-tiles of its M-tile at 64 edges, its two M-tiles at 32),
+// and each takes  am_t += Whi.Xhi,  al_t += Whi.Xlo',  al_t += Wlo'.Xhi.  An issue order is a table of (A image, B image, tile); the product goes to am_t when
+// both images are hi, to al_t otherwise.  Every accumulator sees its own products in the same order in all of them: same bits.
+//   0: am0 am1 al0 al1 al0 al1   rounds 1-5
+//   1: al0 al1 am0 al0 al1 am1   round 6: the two visits of an `al` accumulator three MFMAs apart instead of two.  With msg0's GEMM (tile_gemm_x3z) in the same
+//                                order QM9 59 110 -> 58 975 cycles per tile of the fused form (-0.25 %; -0.4 % on a second box), GEOM 58 075 -> 57 845 (-0.4 %)
+//                                (profiles/r06_ab_log.txt run 13).  The same reorder in the gate contraction costs +0.6 % and stays out.
+//   3: al0 am0 al1 al0 am1 al1   every distance >= 3 as well: +0.2 % at QM9, -0.3 % at GEOM against order 1 (the third such order, am0 al0 al1 am1 al0 al1, was
+//                                +0.1 % at QM9 and no instantiation takes it)
+// Which instantiation takes which: X3_RO in the kernel.
+struct X3Prod {
+    bool a_lo, b_lo;
+    int t;
+};
+template <int ORDER> struct X3Order;
+template <> struct X3Order<0> { static constexpr X3Prod P[6] = {{false, false, 0}, {false, false, 1}, {false, true, 0}, {false, true, 1}, {true, false, 0}, {true, false, 1}}; };
+template <> struct X3Order<1> { static constexpr X3Prod P[6] = {{false, true, 0}, {false, true, 1}, {false, false, 0}, {true, false, 0}, {true, false, 1}, {false, false, 1}}; };
+template <> struct X3Order<3> { static constexpr X3Prod P[6] = {{false, true, 0}, {false, false, 0}, {false, true, 1}, {true, false, 0}, {false, false, 1}, {true, false, 1}}; };
+// ZM / ZL: this is the first k-block and am / al start from the MFMA's inline zero C operand (al's first product of a block is the one with the hi A image)
+template <int ORDER, bool ZM, bool ZL, int MT, int NT>
+__device__ __forceinline__ void x3_block_mfmas(f32x16 (&am)[MT][NT], f32x16 (&al)[MT][NT], const h8 (&ah)[MT], const h8 (&alo)[MT], const h8 (&bh)[NT], const h8 (&bl)[NT]) {
+    static_assert(MT * NT == 2, "two output tiles per wave");
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    static_for<0, 6>([&](auto ic) {
+        constexpr X3Prod p = X3Order<ORDER>::P[decltype(ic)::value];
+        constexpr int m = NT == 2 ? 0 : p.t, n = NT == 2 ? p.t : 0;
+        const h8& a = p.a_lo ? alo[m] : ah[m];
+        const h8& b = p.b_lo ? bl[n] : bh[n];
+        if constexpr (!p.a_lo && !p.b_lo) am[m][n] = MFMA16(a, b, ZM ? zero : am[m][n]);
+        else al[m][n] = MFMA16(a, b, (ZL && !p.a_lo) ? zero : al[m][n]);
+    });
+}
+
 // TAIL SKEW (round 4) of a two-N-tile GEMM: the last two k-blocks r0, r0 + 1 run N-tile 0 first (6 MFMAs), then N-tile 1 (6 MFMAs) with `tail()` -- the
 // SiLU of N-tile 0's finished accumulators -- issued between them: a wave's own VALU / transcendental instructions cost ~1-3 clk between its MFMAs
 // instead of 4 / ~11 in a VALU phase (profiles/r04_overlap_experiments.md).  Both blocks' A operands are in the ring anyway (PD = 2), the B operands
@@ -443,7 +437,6 @@ __device__ __forceinline__ void tile_gemm_x3z(f32x16 (&am)[MT][NT], f32x16 (&al)
     const h8* sh = xh8 + boff;
     const h8* sl = xl8 + boff;
     h8 bh[2][NT], bl[2][NT];
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int n = 0; n < NT; ++n) { bh[0][n] = sh[n * 32]; bl[0][n] = sl[n * 32]; }
     static_for<0, KBL>([&](auto rc) {
@@ -465,31 +458,8 @@ __device__ __forceinline__ void tile_gemm_x3z(f32x16 (&am)[MT][NT], f32x16 (&al)
 #pragma unroll
             for (int n = 0; n < NT; ++n) { bh[(r + 1) & 1][n] = sh[(r + 1) * 2 * TP + n * 32]; bl[(r + 1) & 1][n] = sl[(r + 1) * 2 * TP + n * 32]; }
         };
-        auto mfmas = [&] {
-#if !defined(GCDM_X3_MFMA_ORDER) || GCDM_X3_MFMA_ORDER >= 1
-            if constexpr (RO >= 1 && MT == 1 && NT == 2) {      // the block's six products in the order of tile_gemm_x3s (round 6: al0 al1 am0 al0 al1 am1; same bits)
-                al[0][0] = MFMA16(ring.ah[r % R][0], bl[r & 1][0], (ZAL && r == 0) ? zero : al[0][0]);
-                al[0][1] = MFMA16(ring.ah[r % R][0], bl[r & 1][1], (ZAL && r == 0) ? zero : al[0][1]);
-                am[0][0] = MFMA16(ring.ah[r % R][0], bh[r & 1][0], (ZAM && r == 0) ? zero : am[0][0]);
-                al[0][0] = MFMA16(ring.alo[r % R][0], bh[r & 1][0], al[0][0]);
-                al[0][1] = MFMA16(ring.alo[r % R][0], bh[r & 1][1], al[0][1]);
-                am[0][1] = MFMA16(ring.ah[r % R][0], bh[r & 1][1], (ZAM && r == 0) ? zero : am[0][1]);
-                return;
-            }
-#endif
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) am[m][n] = MFMA16(ring.ah[r % R][m], bh[r & 1][n], (ZAM && r == 0) ? zero : am[m][n]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) al[m][n] = MFMA16(ring.ah[r % R][m], bl[r & 1][n], (ZAL && r == 0) ? zero : al[m][n]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) al[m][n] = MFMA16(ring.alo[r % R][m], bh[r & 1][n], al[m][n]);
-        };
+        // (msg0's GEMM knows two orders: 1 wherever the residual GEMMs take a new one)
+        auto mfmas = [&] { x3_block_mfmas<(RO >= 1 && MT == 1 && NT == 2) ? 1 : 0, ZAM && r == 0, ZAL && r == 0>(am, al, ring.ah[r % R], ring.alo[r % R], bh[r & 1], bl[r & 1]); };
         // the next blocks' operand requests ride between this block's MFMAs (see tile_gemm_x3s)
         static_assert(PD >= 2, "interleaved requests are waited for one block later: two blocks of prefetch distance");
         x3_wait_block<2 * MT * (PD - 1)>();
@@ -949,84 +919,26 @@ __device__ __forceinline__ void tile_gemm_x3s(f32x16 (&am)[MT][NT], f32x16 (&al)
     const h8* sh = xh8 + boff;
     const h8* sl = xl8 + boff;
     h8 bh[2][NT], bl[2][NT];
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int n = 0; n < NT; ++n) { bh[0][n] = sh[n * 32]; bl[0][n] = sl[n * 32]; }
     auto body = [&](auto rc, auto hooked) {
         constexpr int r = decltype(rc)::value;
         constexpr bool HK = decltype(hooked)::value;
         auto loads = [&] {
-#ifndef GCDM_ABL_NOWLOAD                         // (timing ablation only: the GEMM without its weight stream)
             // uniform base + compile-time block offset + lane: no per-block VALU pointer arithmetic.  Issue order: the operand of the
             // block's FIRST MFMA (ah[0]) last, so that one s_waitcnt covers the whole block instead of one per operand
 #pragma unroll
             for (int m = MT - 1; m >= 0; --m) ring.alo[(r + PD) % R][m] = wp.template ldk<r + PD>(wL + m * wstride * 16);
 #pragma unroll
             for (int m = MT - 1; m >= 0; --m) ring.ah[(r + PD) % R][m] = wp.template ldk<r + PD>(wH + m * wstride * 16);
-#endif
         };
         auto breads = [&] {
-#ifndef GCDM_ABL_NOB
             if constexpr (r + 1 != SPLIT) {          // the block behind the barrier is read after the barrier
 #pragma unroll
                 for (int n = 0; n < NT; ++n) { bh[(r + 1) & 1][n] = sh[(r + 1) * 2 * TP + n * 32]; bl[(r + 1) & 1][n] = sl[(r + 1) * 2 * TP + n * 32]; }
             }
-#else
-            for (int n = 0; n < NT; ++n) { bh[(r + 1) & 1][n] = bh[r & 1][n]; bl[(r + 1) & 1][n] = bl[r & 1][n]; }
-#endif
         };
-        auto mfmas = [&] {
-#if (!defined(GCDM_X3_MFMA_ORDER) || GCDM_X3_MFMA_ORDER >= 1) && !defined(GCDM_ABL_MFMA1)
-            // Round 6: the block's six products in the order al0 al1 am0 al0 al1 am1 -- the two visits of an `al` accumulator three MFMAs apart instead of two
-            // (am0 am1 al0 al1 al0 al1 before; -DGCDM_X3_MFMA_ORDER=0).  Every accumulator still sees its products in the same order: same bits; with msg0's GEMM
-            // (tile_gemm_x3z) in the same order QM9 59 110 -> 58 975 cycles per tile of the fused form (-0.25 %; -0.4 % on a second box), GEOM 58 075 -> 57 845 (-0.4 %)
-            // (profiles/r06_ab_log.txt run 13).  The same reorder in the gate contraction costs +0.6 % and stays out; the two other orders with every distance >= 3
-            // (am0 al0 al1 am1 al0 al1; al0 am0 al1 al0 am1 al1) are +0.1 / +0.2 % at QM9 (the second -0.3 % at GEOM).  RO: which instantiations take the new order (X3_RO in
-            // the kernel) -- the two-launch form of the 8-channel edge width is 0.3 % FASTER in the old one (57 150 against 57 325 cycles), its fused form and both forms of the
-            // 16-channel width in the new one (58 755 -> 58 490 two-launch QM9); its fused form is another 0.3 % faster in the third order (RO = 3).
-            if constexpr (RO == 1 && MT == 1 && NT == 2) {
-                al[0][0] = MFMA16(ring.ah[r % R][0], bl[r & 1][0], r == 0 ? zero : al[0][0]);
-                al[0][1] = MFMA16(ring.ah[r % R][0], bl[r & 1][1], r == 0 ? zero : al[0][1]);
-                am[0][0] = MFMA16(ring.ah[r % R][0], bh[r & 1][0], r == 0 ? zero : am[0][0]);
-                al[0][0] = MFMA16(ring.alo[r % R][0], bh[r & 1][0], al[0][0]);
-                al[0][1] = MFMA16(ring.alo[r % R][0], bh[r & 1][1], al[0][1]);
-                am[0][1] = MFMA16(ring.ah[r % R][0], bh[r & 1][1], r == 0 ? zero : am[0][1]);
-                return;
-            } else if constexpr (RO == 2 && MT == 1 && NT == 2) {      // am0 al0 al1 am1 al0 al1
-                am[0][0] = MFMA16(ring.ah[r % R][0], bh[r & 1][0], r == 0 ? zero : am[0][0]);
-                al[0][0] = MFMA16(ring.ah[r % R][0], bl[r & 1][0], r == 0 ? zero : al[0][0]);
-                al[0][1] = MFMA16(ring.ah[r % R][0], bl[r & 1][1], r == 0 ? zero : al[0][1]);
-                am[0][1] = MFMA16(ring.ah[r % R][0], bh[r & 1][1], r == 0 ? zero : am[0][1]);
-                al[0][0] = MFMA16(ring.alo[r % R][0], bh[r & 1][0], al[0][0]);
-                al[0][1] = MFMA16(ring.alo[r % R][0], bh[r & 1][1], al[0][1]);
-                return;
-            } else if constexpr (RO == 3 && MT == 1 && NT == 2) {      // al0 am0 al1 al0 am1 al1
-                al[0][0] = MFMA16(ring.ah[r % R][0], bl[r & 1][0], r == 0 ? zero : al[0][0]);
-                am[0][0] = MFMA16(ring.ah[r % R][0], bh[r & 1][0], r == 0 ? zero : am[0][0]);
-                al[0][1] = MFMA16(ring.ah[r % R][0], bl[r & 1][1], r == 0 ? zero : al[0][1]);
-                al[0][0] = MFMA16(ring.alo[r % R][0], bh[r & 1][0], al[0][0]);
-                am[0][1] = MFMA16(ring.ah[r % R][0], bh[r & 1][1], r == 0 ? zero : am[0][1]);
-                al[0][1] = MFMA16(ring.alo[r % R][0], bh[r & 1][1], al[0][1]);
-                return;
-            }
-#endif
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) am[m][n] = MFMA16(ring.ah[r % R][m], bh[r & 1][n], r == 0 ? zero : am[m][n]);
-#ifndef GCDM_ABL_MFMA1
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) al[m][n] = MFMA16(ring.ah[r % R][m], bl[r & 1][n], r == 0 ? zero : al[m][n]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) al[m][n] = MFMA16(ring.alo[r % R][m], bh[r & 1][n], al[m][n]);
-#else
-            if (r == 0) { for (int m = 0; m < MT; ++m) for (int n = 0; n < NT; ++n) al[m][n] = zero; }
-#endif
-        };
+        auto mfmas = [&] { x3_block_mfmas<(MT == 1 && NT == 2) ? RO : 0, r == 0, r == 0>(am, al, ring.ah[r % R], ring.alo[r % R], bh[r & 1], bl[r & 1]); };
         if constexpr (!HK) {
             // the next blocks' operand requests ride BETWEEN this block's MFMAs (one per MFMA: B reads first, their latency is the shorter
             // one to cover), issued while the matrix pipe works on the MFMA in front of them, instead of in a burst ahead of the block
@@ -1071,14 +983,6 @@ __device__ __forceinline__ void tile_gemm_x3s(f32x16 (&am)[MT][NT], f32x16 (&al)
         x3_tail_skew<PD, SPLIT>(am, al, ring, bh, bl, sh, sl, TP, tail);        // (see x3_tail_skew)
     }
 }
-
-struct AblFmaFill {                   // (GCDM_ABL_VECFMA: 24 independent FMAs per hooked stage)
-    float x[24];
-    __device__ __forceinline__ void run() {
-#pragma unroll
-        for (int i = 0; i < 24; ++i) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(x[i]) : "v"(1.0001f), "v"(0.0003f));
-    }
-};
 
 struct EdgeMsgX3Args {
     X3Const x3c;                      // MUST stay the first member (X3_KARG)
@@ -1131,7 +1035,7 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using Geo = EdgeGeo<ET>;
     constexpr int ETP = Geo::TP, EK_THREADS = Geo::THREADS, PARTS = Geo::PARTS;
-    // MFMA order inside a k-block of the tile GEMMs (tile_gemm_x3s: 0 = am0 am1 al0 al1 al0 al1, 1 = al0 al1 am0 al0 al1 am1, 3 = al0 am0 al1 al0 am1 al1), measured per
+    // MFMA order inside a k-block of the tile GEMMs (x3_block_mfmas: 0 = am0 am1 al0 al1 al0 al1, 1 = al0 al1 am0 al0 al1 am1, 3 = al0 am0 al1 al0 am1 al1), measured per
     // instantiation: 16-channel edge width 1 in both forms; 8-channel: two-launch form 0 (57 130 cycles; 1: 57 325, 2: 57 250, 3: 57 220), fused form 3 (57 690; 1: 57 880, 0: 58 030)
     constexpr int X3_RO = VE == 16 ? 1 : (TR::ON ? 3 : 0);
     constexpr int X3_GROUPS8 = 36;                      // 32 state + 1 norm + 2 frame scalars + 1 pad (K' = 288)
@@ -1193,11 +1097,7 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     // edge (node) index, array base and row stride are scalars -- no 64-bit VALU address arithmetic per load
     const BufView ws = make_view(ax0.wspool, ax0.wspool_bytes);
     const BufView wv = make_view(ax0.wpool, ax0.wpool_bytes);
-#ifdef GCDM_X3_SAUX
-    constexpr int SAUX = GCDM_X3_SAUX;
-#else
     constexpr int SAUX = SE == 64 ? 2 : 0;               // cache policy of the streamed per-edge constants (BufView::ld1s)
-#endif
     constexpr int EPN = (SE / 4) / PARTS;                // e' float4 groups per thread (QM9 2, GEOM: parts 0..3 one each)
     constexpr int EPN1 = EPN > 0 ? EPN : 1;
     const uint32_t rowE = (uint32_t)E * 4u, rowN = (uint32_t)N * 4u;
@@ -1232,57 +1132,33 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     };
     auto load_const = [&](auto pc, const EdgeMsgArgs& a, const Who& w, int tile, TileIn& in) {       // independent of the edge list; three bursts (P = 0, 1, 2; P < 0: all)
         constexpr int P = decltype(pc)::value;
-#ifdef GCDM_ABL_NOCONST      // (timing ablation, round 5: the tile WITHOUT [some of] its 368 B per edge of streamed constants -- the ceiling of what recomputing them per layer could return)
-        // GCDM_ABL_NOCONST = bit mask of the streams replaced by constants: 1 FR, 2 EP4, 4 AL (alpha), 8 U
-        constexpr int ABL = GCDM_ABL_NOCONST;
-#else
-        constexpr int ABL = 0;
-#endif
-        if constexpr ((ABL & 1) != 0 && (P < 0 || P == 0)) { for (int r = 0; r < 9; ++r) in.fr[r] = 0.01f * (r + 1); }
-        if constexpr ((ABL & 2) != 0 && (P < 0 || P == 1)) { for (int i = 0; i < EPN1; ++i) in.epv[i] = (v4f){0.1f, -0.2f, 0.3f, 0.05f}; }
-        if constexpr ((ABL & 4) != 0 && (P < 0 || P == 1)) { for (int j = 0; j < 8; ++j) in.av[j] = 0.02f * j; }
-        if constexpr ((ABL & 4) != 0 && (P < 0 || P == 2)) { for (int c = 0; c < (BETA_MFMA ? 1 : VE); ++c) in.al[c] = 0.03f; }
-        if constexpr ((ABL & 8) != 0 && (P < 0 || P == 2)) { in.u0 = 0.6f; in.u1 = 0.0f; in.u2 = 0.8f; }
         const int e0 = tile * ET, eid = min(e0 + w.e, E - 1);
         const uint32_t ve4 = (uint32_t)eid * 4u, ve16 = (uint32_t)eid * 16u;
-#ifndef GCDM_X3_AL_AUX
-#define GCDM_X3_AL_AUX SAUX
-#endif
-#ifndef GCDM_X3_AV_BURST
-#define GCDM_X3_AV_BURST 1
-#endif
-        if constexpr ((ABL & 4) == 0 && (P < 0 || P == GCDM_X3_AV_BURST) && BETA_MFMA && GCDM_X3_AV_BURST == 0) {
-            if (w.wave >= ET / 8 - ET / 32) {
-                const uint32_t eg4 = (uint32_t)min(e0 + 32 * (w.wave - (ET / 8 - ET / 32)) + (w.lane & 31), E - 1) * 4u + (uint32_t)(8 * (w.lane >> 5)) * rowE, o = ws.off(a.AL);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) in.av[j] = ws.template ld1s<GCDM_X3_AL_AUX>(eg4, o + (uint32_t)j * rowE);
-            }
-        }
-        if constexpr ((ABL & 1) == 0 && (P < 0 || P == 0)) {
+        if constexpr (P < 0 || P == 0) {
             const uint32_t o = ws.off(a.FR);
 #pragma unroll
             for (int r = 0; r < 9; ++r) in.fr[r] = w.need_fr ? ws.template ld1s<SAUX>(ve4, o + r * rowE) : 0.f;
         }
-        if constexpr ((ABL & 2) == 0 && (P < 0 || P == 1)) {
+        if constexpr (P < 0 || P == 1) {
             const uint32_t o = ws.off(a.EP4);
 #pragma unroll
             for (int i = 0; i < EPN1; ++i)
                 in.epv[i] = ws.template ld4s<SAUX>(ve16 + (uint32_t)min(w.part + PARTS * i, SE / 4 - 1) * (rowE * 4u), o);          // the group index depends on the lane's part
         }
-        if constexpr ((ABL & 4) == 0 && (P < 0 || P == 2) && !BETA_MFMA) {
+        if constexpr ((P < 0 || P == 2) && !BETA_MFMA) {
             const uint32_t o = ws.off(a.AL);
 #pragma unroll
             for (int c = 0; c < VE; ++c) in.al[c] = ws.template ld1s<SAUX>(ve4, o + c * rowE);
         }
-        if constexpr ((ABL & 4) == 0 && (P < 0 || P == 1) && BETA_MFMA && GCDM_X3_AV_BURST != 0) {
+        if constexpr ((P < 0 || P == 1) && BETA_MFMA) {
             if (w.wave >= ET / 8 - ET / 32) {         // the LAST waves contract beta: they are the first to leave the previous tile's segment sums
                 // (the half of K this lane holds rides in the per-lane offset: a lane-dependent scalar offset would cost a waterfall loop per load)
                 const uint32_t eg4 = (uint32_t)min(e0 + 32 * (w.wave - (ET / 8 - ET / 32)) + (w.lane & 31), E - 1) * 4u + (uint32_t)(8 * (w.lane >> 5)) * rowE, o = ws.off(a.AL);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) in.av[j] = ws.template ld1s<GCDM_X3_AL_AUX>(eg4, o + (uint32_t)j * rowE);
+                for (int j = 0; j < 8; ++j) in.av[j] = ws.template ld1s<SAUX>(eg4, o + (uint32_t)j * rowE);
             }
         }
-        if constexpr ((ABL & 8) == 0 && (P < 0 || P == 2)) {
+        if constexpr (P < 0 || P == 2) {
             const uint32_t oU = ws.off(a.U);
             if (w.need_fr) { in.u0 = ws.template ld1s<SAUX>(ve4, oU); in.u1 = ws.template ld1s<SAUX>(ve4, oU + rowE); in.u2 = ws.template ld1s<SAUX>(ve4, oU + 2 * rowE); }
             else { in.u0 = 0.f; in.u1 = 0.f; in.u2 = 0.f; }
@@ -1313,13 +1189,9 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         static_for<C * NVD / GCH, (C + 1) * NVD / GCH>([&](auto vc) {
             constexpr int f = decltype(vc)::value, which = f & 1, x = (f >> 1) % 3, i = (f >> 1) / 3;
             const int hh = min(w.part + PARTS * i, ROWS0 - 1);                                      // the row depends on the lane's part
-#ifdef GCDM_ABL_NOGATHER
-            if (which) in.gj[i][x] = 0.2f; else in.gi[i][x] = 0.1f * x;
-#else
             const uint32_t v = ((uint32_t)(hh * 3) * N + (which ? ix.nj : ix.ni)) * 4u;
             if (which) in.gj[i][x] = ws.ld1(v, oJ + x * rowN);
             else in.gi[i][x] = ws.ld1(v, oI + x * rowN);
-#endif
         });
         if (C == GCH - 1) in.ncnt = w.wave == 0 ? a.NCNT[ix.ni] : 0;
     };
@@ -1357,7 +1229,6 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     float* US = (float*)(smem + Geo::OFF_US);            // [3][ETP]: the edges' unit vectors (staged by the last part, read by everyone behind the barrier)
 
     // ---- P1: msg0 pre-phase ---------------------------------------------------------------------------------------------
-#ifndef GCDM_ABL_NOP1
     {
         float* BETA = PG;                                   // [ET][33]: BETA[e * 33 + h]
         load_pq_part(std::integral_constant<int, 0>{}, a, me, ix, in);
@@ -1414,12 +1285,8 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             if constexpr (!BETA_MFMA) {
                 const uint32_t vW = (uint32_t)(hh * VE) * 4u;
                 float bsum = 0.f;
-#ifdef GCDM_ABL_NOBETA
-                bsum = in.al[0];
-#else
 #pragma unroll
                 for (int c = 0; c < VE; ++c) bsum += wv.ld1(vW, oW + c * 4) * in.al[c];
-#endif
                 beta[i] = bsum;
             }
             beta2[i] = 0.f;
@@ -1500,10 +1367,6 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             const float vx = in.gi[i][0] + beta[i] * u0 + beta2[i] * s0 + in.gj[i][0];
             const float vy = in.gi[i][1] + beta[i] * u1 + beta2[i] * s1 + in.gj[i][1];
             const float vz = in.gi[i][2] + beta[i] * u2 + beta2[i] * s2 + in.gj[i][2];
-#ifdef GCDM_ABL_NOP1W
-            if (vx + vy + vz == 123.456f) VH[e] = vx;
-            continue;
-#endif
             if (hh < H0) {
                 over |= put16(XH, XL, ETP, N8 + (hh >> 3), hh & 7, e, fast_sqrt(vx * vx + vy * vy + vz * vz + 1e-8f) + 1e-8f);
                 VH[(hh * 3 + 0) * ETP + e] = vx;
@@ -1521,12 +1384,10 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         }
         static_for<(NH0 < 3 ? 4 + NH0 : 7), GCH>([&](auto cc) { load_pq_part(cc, a, me, ix, in); });
         if (part == PARTS - 1) {
-            // the slots no row is written to: between the norms and the frame scalars (padded layout only), and behind the last frame scalar
-            for (int pos = SE + H0; pos < QPOS; ++pos) put16(XH, XL, ETP, pos >> 3, pos & 7, e, 0.f);
+            // the slots no row is written to: behind the last frame scalar
             for (int pos = QPOS + 9; pos < 16 * KB0C; ++pos) put16(XH, XL, ETP, pos >> 3, pos & 7, e, 0.f);
         }
     }
-#endif
     STAMP(1);
     if constexpr (TR::ON) x3_wait_block<0>();      // every store of the PREVIOUS tile's segment sums has been acknowledged by the L2 (the loads still in flight -- msg0's
                                                    // first weight blocks, the PQ rows -- are consumed right behind the barrier anyway)
@@ -1566,14 +1427,10 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
-#ifdef GCDM_ABL_NOPQ
-                    for (int t = 0; t < 4; ++t) am[m][n][4 * q + t] = 0.f;
-#else
                     for (int t = 0; t < 4; t += 2) {
                         const f32x2 s2 = pk_add((f32x2){in.pqi[m][n][q][t], in.pqi[m][n][q][t + 1]}, (f32x2){in.pqj[m][n][q][t], in.pqj[m][n][q][t + 1]});
                         am[m][n][4 * q + t] = s2[0]; am[m][n][4 * q + t + 1] = s2[1];
                     }
-#endif
         STAMP(3);
         constexpr int SILU0_N0 = (NT == 2 && MT == 1) ? 1 : 0;       // N-tile 0's SiLU rides in the GEMM's tail (x3_tail_skew)
         if constexpr (SILU0_N0) {
@@ -1592,7 +1449,6 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
             for (int n = SILU0_N0; n < NT; ++n) silu_merge16(st[m][n], am[m][n], al2[m][n], X3_INV_SCALE);
         STAMP(5);
-#ifndef GCDM_ABL_NOGATE
         gate_partial_x3p<MT, NT, true>(gm, gl, st, gw0);
         if (NW == 4) {               // four partials = the four slots the vector waves sum: no fold needed
             put_gate_partial<NT, ET>(PG, gm, gl, wave, lane, false);
@@ -1601,15 +1457,12 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             __syncthreads();         // also: every wave is done reading the msg0 operand images
             if (wave >= 4) put_gate_partial<NT, ET>(PG, gm, gl, wave - 4, lane, true);
         }
-#endif
         STAMP(6);
     }
     if (NW == 4) __syncthreads();
     STAMP(7);
     // ---- P3: state images ---------------------------------------------------------------------------------------------------
-#ifndef GCDM_ABL_NOSTORE
     store_state_x3<MT, NT>(XH, XL, 0, st, ETP, mt0, lane, amax);
-#endif
     STAMP(8);
     __syncthreads();
     STAMP(9);
@@ -1632,16 +1485,7 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             vs.fA = k == 0 ? ax.vf0H : ax.vf1[k == 0 ? 0 : k - 1]; vs.fB = k == 0 ? ax.vf0L : ax.vf2[k == 0 ? 0 : k - 1];
             vs.pH = ax.vpH[k]; vs.pL = ax.vpL[k];
             vs.ve = ve; vs.vq = vq; vs.lane = lane;
-#ifdef GCDM_ABL_VECFMA       // (timing ablation: the hooked stages replaced by the same number of INDEPENDENT fp32 FMAs -- is it the instruction count or the stages' dependency structure?)
-            AblFmaFill fx_;
-            for (int i = 0; i < 24; ++i) fx_.x[i] = 0.001f * (lane + i);
-            tile_gemm_x3s<MT, NT, PD, 18, 16, true, X3_RO>(am, al2, ring, wp, gwH, gwL, xh8, xl8, ETP, lane, [&](auto) { fx_.run(); }, silu_n0);
-            amax = fmaxf(amax, fx_.x[0] * 1e-30f + fx_.x[23] * 1e-30f);
-#elif defined(GCDM_ABL_VECNONE)
-            tile_gemm_x3s<MT, NT, PD, 18, 16, true, X3_RO>(am, al2, ring, wp, gwH, gwL, xh8, xl8, ETP, lane, [&](auto) {}, silu_n0);
-#else
             tile_gemm_x3s<MT, NT, PD, 18, 16, true, X3_RO>(am, al2, ring, wp, gwH, gwL, xh8, xl8, ETP, lane, [&](auto rc) { vs.template run<decltype(rc)::value>(); }, silu_n0);
-#endif
             amax = fmaxf(amax, vs.amax);
         } else {
             tile_gemm_x3s<MT, NT, PD, 18, 16, false, X3_RO>(am, al2, ring, wp, gwH, gwL, xh8, xl8, ETP, lane, [](auto) {}, silu_n0);
@@ -1656,38 +1500,29 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #pragma unroll
             for (int n = SILU_N0; n < NT; ++n) silu_merge16(am[m][n], am[m][n], al2[m][n], X3_INV_SCALE);
         if (k == GCDM_STAMP_K) STAMP(13);
-        [[maybe_unused]] h8 fin_w1[2], fin_w2[2];
-#ifndef GCDM_ABL_NOGATE
+        h8 fin_w1[2], fin_w2[2];
         gate_partial_x3p<MT, NT, true>(gm, gl, am, gwk);
         // the next tile (clamped to the workgroup's last one: no branch): its index words and per-edge constants are requested behind the last
         // gate contraction (its operands are dead) and arrive under the fold of the gate partials and the state image; the gathers that need the index words are dealt out
         // over the attention phase (load_gather_part) and arrive under the aggregation
         // the vector_up operands of the last GCP2's vector part (finish_only below) are requested ahead of the next tile's index words and constants: loads
-        // return in order, so behind those HBM streams they would wait for them (-DGCDM_X3_FIN_LATE: requested at the point of use, rounds 1-4)
-#ifndef GCDM_X3_FIN_LATE
+        // return in order, so behind those HBM streams they would wait for them (rounds 1-4 requested them at the point of use)
         if (k == 2 && vhalf == 1) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) { fin_w1[j] = wp.ld(wp.off(ax.vf1[2] + 64 * j)); fin_w2[j] = wp.ld(wp.off(ax.vf2[2] + 64 * j)); }
         }
-#endif
         if (k == 2) {
             nxt_tile = start_ + min(it_ + stride_, cnt_ - 1);
             ix = load_idx(a, me, nxt_tile);
             load_const(std::integral_constant<int, 0>{}, a, me, nxt_tile, in);      // (in three bursts with the fold / the residual add between them)
         }
-#ifdef GCDM_ABL_GATE_NOPG
-        asm volatile("" ::"v"(gm[0]), "v"(gl[0]));
-        if (false) {
-#else
         if (NW == 4) {
-#endif
             put_gate_partial<NT, ET>(PG, gm, gl, wave, lane, false);
         } else {
             if (wave < 4) put_gate_partial<NT, ET>(PG, gm, gl, wave, lane, false);
             __syncthreads();         // also: every wave is done reading the old XH8 / XL8 images
             if (wave >= 4) put_gate_partial<NT, ET>(PG, gm, gl, wave - 4, lane, true);
         }
-#endif
         if (k == GCDM_STAMP_K) STAMP(14);
         // 4 waves: every wave is done reading the old images; gate partials complete.  8 waves: the barrier inside the fold said the first, and
         // the partials are complete at the barrier behind the state images (last GCP2: behind the attention partials)
@@ -1705,9 +1540,7 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 }
         if (k == 2) load_const(std::integral_constant<int, 2>{}, a, me, nxt_tile, in);
         if (k < 2) {
-#ifndef GCDM_ABL_NOSTORE
             store_state_x3<MT, NT>(XH, XL, 0, st, ETP, mt0, lane, amax);
-#endif
         } else {
             // last GCP2: scalar message attention (gcpnet.py:703-707) on the registers.  Each wave contracts its 32 channels of the final state
             // with the attention weights (WAX4, staged once per workgroup; the two lane halves hold different channels of the same edge), the
@@ -1739,13 +1572,7 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 vs.PG = PG; vs.bg = a.mk[2].bg; vs.FR = FR; vs.VH = VH; vs.VHB = VHB; vs.VV4 = VV4; vs.XH = XH; vs.XL = XL;
                 vs.fA = ax.vf1[2]; vs.fB = ax.vf2[2]; vs.pH = nullptr; vs.pL = nullptr;
                 vs.ve = ve; vs.vq = vq; vs.lane = lane;
-#ifndef GCDM_X3_FIN_LATE
                 vs.w1[0] = fin_w1[0]; vs.w1[1] = fin_w1[1]; vs.w2[0] = fin_w2[0]; vs.w2[1] = fin_w2[1]; vs.preloaded = true;
-#endif
-#ifdef GCDM_ABL_FINW        // (timing ablation, round 5: the last vector part WITHOUT its four operand loads, which are issued behind the next tile's HBM prefetches and return in order)
-                { const h8 c_ = {(_Float16)0.01f, (_Float16)0.02f, (_Float16)0.03f, (_Float16)0.01f, (_Float16)0.02f, (_Float16)0.03f, (_Float16)0.01f, (_Float16)0.02f};
-                  vs.w1[0] = c_; vs.w1[1] = c_; vs.w2[0] = c_; vs.w2[1] = c_; vs.preloaded = true; }
-#endif
                 vs.finish_only();
             }
             float att[NT];
@@ -1783,7 +1610,6 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if (__any(over) && lane == 0) atomicOr(ax.flags_dev, GCDM_FLAG_F16_RANGE_BIT);
 
     // ---- aggregation: segment sums of the attention-weighted messages (fp32 data) -------------------------------------------------------
-#ifndef GCDM_ABL_NOAGG
     STAMP(19);
     {
         const int nseg = m_misc[0];
@@ -1796,12 +1622,8 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         // one after the other.  Same sums in the same order per item: same bits.
         const int nscal = nseg * GCDM_SG;
         for (int wk = tid; wk < nseg * UNITS; wk += EK_THREADS) {
-#ifdef GCDM_X3_AGG_BY_SEGMENT
-            const int sg = wk / UNITS, un = wk - sg * UNITS;
-#else
             const int rv = wk - nscal;
             const int sg = wk < nscal ? wk / GCDM_SG : rv / (UNITS - GCDM_SG), un = wk < nscal ? wk - sg * GCDM_SG : GCDM_SG + rv - sg * (UNITS - GCDM_SG);
-#endif
             const int2 rec = m_rec[sg];
             const int node = rec.x, sb = rec.y & 255, en = (rec.y >> 8) & 255;
             const bool whole = (rec.y >> 16) != 0;
@@ -1833,7 +1655,6 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             }
         }
     }
-#endif
     STAMP_END(20);
     it_ += stride_;
     if (it_ >= cnt_) break;

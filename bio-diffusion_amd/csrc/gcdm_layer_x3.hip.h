@@ -37,7 +37,7 @@
 // Counters are self-resetting (the consumer of a node tile zeroes its counter; the last workgroup to leave zeroes the cursors and arrival words), so a captured
 // step graph replays the same kernel arguments.
 #pragma once
-#include "gcdm_node_x3w.hip.h"
+#include "gcdm_node_x3.hip.h"
 
 #define GCDM_FLAG_TAIL_BIT (16u | GCDM_FLAG_F16_RANGE_BIT)      // raised together with the range flag: every caller's existing re-run (fp32 mode, two launches per layer) repairs the result
 
@@ -52,13 +52,14 @@ struct TailArgs {
 };
 constexpr int TAIL_CTR_WORDS = 25;
 
-template <int T>                   // nodes per node tile: 32 (node_tile_x3) or 64 (node_tile_x3w)
+template <int T>                   // nodes per node tile: 32 (node_tile_x3)
 struct NodeTailRole {
+    static_assert(T == 32, "the tail role runs 32-node tiles (64-node tiles cost the edge role a register: gcdm_api.hip, launch of the fused layer)");
     static constexpr bool ON = true;
-    static constexpr int LOG_T = T == 64 ? 6 : 5;
+    static constexpr int LOG_T = 5;
     static constexpr int SPIN_LIMIT = 1 << 20;          // x ~0.5 us: far beyond any launch; then the flag, never a hang
     struct Args { EdgeMsgX3Args e; TailArgs t; };
-    static constexpr int NODE_LDS = T == 64 ? NW_LDS_BYTES : NK_LDS_BYTES;
+    static constexpr int NODE_LDS = NK_LDS_BYTES;
     static constexpr int WORD_OFF = EdgeGeo<64>::LDS_BYTES_X3 > NODE_LDS ? EdgeGeo<64>::LDS_BYTES_X3 : NODE_LDS;
     static constexpr int LDS_BYTES = WORD_OFF + 16;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
@@ -137,8 +138,7 @@ struct NodeTailRole {
             if (t < 0) break;
             int tidn = threadIdx.x;
             asm volatile("" : "+v"(tidn));
-            if constexpr (T == 64) node_tile_x3w(ta.nx, smem, t, tidn);
-            else node_tile_x3<false, 2>(ta.nx, smem, t, tidn);
+            node_tile_x3<false, 2>(ta.nx, smem, t, tidn);
         }
         int tide = threadIdx.x;
         asm volatile("" : "+v"(tide));

@@ -200,7 +200,7 @@ int gcdm_debug_set_layer_limit(gcdm_handle* h, int32_t num_layers_to_run);
  * "fuse_node": 1 (default; env GCDM_FUSE_NODE) / 0 -- split-precision mode, persistent 64-edge launches, unmasked plans: a layer is ONE launch, its node tiles run
  * as a tail role of the persistent edge-message workgroups (csrc/gcdm_layer_x3.hip.h: readiness counters per node tile, self-resetting; safe when several handles
  * share the GPU -- the node role is entered only when every workgroup of the XCD group has arrived -- but then SLOWER than two launches per layer: set 0 on handles
- * that run concurrently, as the package's slice / lane handles do).  Same bits.  "fuse_tile": nodes per node tile of that tail role (32; 0 = automatic).
+ * that run concurrently, as the package's slice / lane handles do).  Same bits.
  * "fuse_active" (read-only): 1 if the last gcdm_forward of the handle used the fused launch.
  * "node_tile": nodes per workgroup of the split-precision per-layer node kernel: 64 (every streamed weight byte feeds two 32-node MFMA tiles), 32, or
  * 0 = automatic (default; env GCDM_NODE_TILE): whichever needs fewer CU rounds for the plan's node count.  Same bits.

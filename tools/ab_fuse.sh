@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of the fused layer launch (node tiles as a tail role of the persistent edge workgroups) on ONE box: GCDM_FUSE_NODE=0|1, GCDM_FUSE_TILE=32|64
+# A/B of the fused layer launch (node tiles as a tail role of the persistent edge workgroups) on ONE box: GCDM_FUSE_NODE=0|1
 #   tools/ab_fuse.sh "qm9 geom"      -> gpurun_out/ab_fuse.log
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}

@@ -1,9 +1,9 @@
 #!/bin/bash
 # Builds kernel variants of libgcdm_hip.so for A/B runs (build container; hipcc cross-compiles gfx950 without a GPU):
-#     tools/build_variants.sh base: stamps:-DGCDM_STAMPS "nogate:-DGCDM_STAMPS -DGCDM_ABLATIONS -DGCDM_ABL_NOGATE"
-# -> build/ab/libgcdm_base.so, build/ab/libgcdm_v3.so   (build/ is git-ignored but travels to the GPU box with gpurun)
+#     tools/build_variants.sh base: stamps:-DGCDM_STAMPS "settle:-DGCDM_STAMPS -DGCDM_X3_SETTLE"
+# -> build/ab/libgcdm_base.so, build/ab/libgcdm_stamps.so, build/ab/libgcdm_settle.so   (build/ is git-ignored)
 # then on the GPU box, same call, alternating:
-#     for v in base v3 base v3; do cp build/ab/libgcdm_$v.so bio-diffusion_amd/libgcdm_hip.so; python tools/ab_variant.py $v qm9 base; done
+#     for v in base settle base settle; do cp build/ab/libgcdm_$v.so bio-diffusion_amd/libgcdm_hip.so; python tools/ab_variant.py $v qm9 base; done
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p build/ab
