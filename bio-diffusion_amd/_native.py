@@ -20,7 +20,8 @@ OPS_LIB_PATH = os.path.join(_HERE, "libgcdm_ops.so")
 OPS_SOURCES = [os.path.join(_HERE, "csrc", "gcdm_ops.hip")]
 OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_ops.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.mp_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_train.h"),
-               os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h")]
+               os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.classifier.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier.h")]
 ABI_VERSION = 2
 
 FLAG_NAN_VEL, FLAG_MEAN_NOT_ZERO, FLAG_COG_DRIFT, FLAG_F16_RANGE = 1, 2, 4, 8
@@ -144,6 +145,15 @@ OPTIM_SIGNATURES = {
 OPTIM_RESTYPES = {"gcdm_optim_workspace_bytes": C.c_int64}
 OPTIM_QUEUE_MAX = 1024          # GCDM_OPTIM_QUEUE_MAX
 OPTIM_FLAG_NONFINITE = 1        # GCDM_OPTIM_FLAG_NONFINITE
+# the EGNN property classifier, forward only (include/gcdm_classifier.h), exported from the same library
+CLASSIFIER_SIGNATURES = {
+    "gcdm_classifier_last_error": [],
+    "gcdm_classifier_workspace_bytes": [I32, I64, I32, I32, I32],
+    "gcdm_classifier_pack": [P, I32, I32, I32, I32, I32, I32, P, P],
+    "gcdm_classifier_forward": [P, P, P, P, P, P, P, I32, I64, I64, I32, I32, I32, I32, P],
+}
+CLASSIFIER_RESTYPES = {"gcdm_classifier_workspace_bytes": C.c_int64, "gcdm_classifier_last_error": C.c_char_p}
+CLASSIFIER_MAX_NODES, CLASSIFIER_MAX_IN_NODE_NF, CLASSIFIER_MAX_HIDDEN_NF = 32, 16, 256      # GCDM_CLASSIFIER_MAX_*
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -155,10 +165,10 @@ def load_ops() -> C.CDLL:
     if not os.path.exists(OPS_LIB_PATH):
         raise RuntimeError(f"{OPS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
     lib = C.CDLL(OPS_LIB_PATH)
-    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
+    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = sig
-        fn.restype = {**MP_TRAIN_RESTYPES, **OPTIM_RESTYPES}.get(name, C.c_int)
+        fn.restype = {**MP_TRAIN_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES}.get(name, C.c_int)
     _ops_lib = lib
     return lib
 

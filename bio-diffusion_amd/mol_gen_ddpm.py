@@ -477,6 +477,49 @@ class _MoleculeGenerationDDPM(nn.Module):
                     account(xh, c[1])
         return self.analyze_samples(torch.cat(results).cpu(), type_counts)
 
+    @torch.inference_mode()
+    def evaluate_conditional(self, classifier: Any, property: str, mean: float, mad: float, iterations: int, batch_size: int,
+                             props_distr: Any = None, unknown_labels: bool = False, save_molecules: bool = False,
+                             sampling_output_dir: Optional[str] = None, **sample_kw) -> Tuple[float, List[Dict[str, Any]]]:
+        """The conditional-evaluation driver, src/mol_gen_eval_conditional_qm9.py:101-156 and :303-315 on the device: per batch draw the sizes,
+        draw the (normalised) context from ``props_distr.sample_batch``, ``sample``, de-normalise the label with ``props_distr.normalizer``
+        (``unknown_labels``: the label is the property's mean), classify the samples (classifier.EGNN.predict: one launch, no copy of the
+        samples) and accumulate ``mean(|mad pred + mean - label|)`` with weight ``batch_size``.  The reference's loader yields while
+        ``i <= iterations``, i.e. ``iterations + 1`` batches; so does this.  ``props_distr`` is duck-typed (``sample_batch``, ``properties``,
+        ``normalizer``) and defaults to ``self.props_distr``.  ``save_molecules`` writes each batch's XYZ files under
+        ``<sampling_output_dir>/run<i>/``.  Returns the MAE and one record per batch (loss, num_nodes, label, pred and the samples x / one_hot,
+        all left on the device)."""
+        if not self.condition_on_context:
+            raise Exception("Conditional evaluation requires a conditional model (module_cfg.conditioning).")
+        props_distr = self.props_distr if props_distr is None else props_distr
+        if props_distr is None:
+            raise ValueError("evaluate_conditional needs props_distr (none attached)")
+        prop_key = props_distr.properties[0]
+        if prop_key != property:
+            raise ValueError(f"props_distr conditions on {prop_key!r}, the classifier is evaluated on {property!r}")
+        norm = props_distr.normalizer[prop_key]
+        total, count, records = 0.0, 0, []
+        for i in range(int(iterations) + 1):
+            num_nodes = self.ddpm.num_nodes_distribution.sample(batch_size)
+            assert int(num_nodes.max()) <= self.dataset_info.get("max_n_nodes", int(num_nodes.max()))
+            context = props_distr.sample_batch(num_nodes).to(self.device)
+            x, one_hot, charges, batch_index = self.sample(num_samples=batch_size, num_nodes=num_nodes, context=context, **sample_kw)
+            if save_molecules:
+                out_dir = os.path.join(str(sampling_output_dir) if sampling_output_dir is not None else "sampling_output", f"run{i}")
+                save_xyz_file(path=out_dir + "/", positions=x, one_hot=one_hot, charges=charges, dataset_info=self.dataset_info,
+                              id_from=i * batch_size, name="conditional", batch_index=batch_index)
+            label = context.reshape(batch_size, -1)[:, 0].to(torch.float32)
+            if unknown_labels:
+                label = torch.full_like(label, float(norm["mean"]))
+            else:
+                label = label * float(norm["mad"]) + float(norm["mean"])
+            pred = classifier.predict(x, one_hot, num_nodes=num_nodes)
+            loss = (mad * pred + mean - label).abs().mean().item()               # one scalar per batch reaches the host
+            total += loss * batch_size
+            count += batch_size
+            records.append(dict(loss=loss, num_nodes=num_nodes, label=label, pred=pred, x=x, one_hot=one_hot))
+        return total / count, records
+
     def analyze_samples(self, stability: torch.Tensor, atom_type_counts: torch.Tensor) -> Dict[str, Any]:
         """qm9_mol_gen_ddpm.py:846-885 on the device results: `stability` int [M, 3] rows (stable, nr_stable_atoms, n)."""
         st = stability.to(torch.int64)
