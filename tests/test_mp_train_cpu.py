@@ -11,6 +11,9 @@ import shutil
 import subprocess
 
 import pytest
+import torch
+
+import mp_train_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pkg = importlib.import_module("bio-diffusion_amd")
@@ -170,3 +173,16 @@ def test_set_message_path_fused_refuses_configurations_outside_the_kernels(over,
     with pytest.raises(NotImplementedError, match=re.escape(reason)):
         net.set_message_path("fused")
     assert net.message_path == "operators"
+
+
+def test_random_sparse_has_the_properties_it_is_there_for():
+    """The graph of tests/test_mp_train_cabi_gpu.py that separates colptr from rowptr: a change of seed must not quietly lose what it is for."""
+    g = mp_train_ref.random_sparse()
+    outdeg, indeg = torch.bincount(g.row, minlength=g.N), torch.bincount(g.col, minlength=g.N)
+    assert g.N == 300 and 1900 <= g.E <= 2100
+    assert bool((g.row[1:] >= g.row[:-1]).all())
+    assert int(((outdeg == 0) & (indeg > 0)).sum()) >= 10 and int(((indeg == 0) & (outdeg > 0)).sum()) >= 10
+    assert outdeg[0] == 0 and indeg[0] == 0 and outdeg[-1] == 0 and indeg[-1] == 0
+    assert (g.row * g.N + g.col).unique().numel() < g.E      # an edge appears twice
+    assert bool((g.row == g.col).any())                      # a self-loop
+    assert not torch.equal(g.rowptr, g.colptr)
