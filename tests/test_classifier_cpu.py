@@ -251,6 +251,76 @@ def test_restatement_against_the_imported_reference_on_fresh_inputs(att, attr):
     assert (cr.forward(W, x, h0, sizes) - ref).abs().max().item() <= 1e-12
 
 
+# ---- the inputs and the bar of tests/test_classifier_cabi_gpu.py ------------------------------------------------------------------------------
+HOT_CASES = [(H, cr.INSTANTIATION_SIZES) for H in range(32, 257, 32)] + [(96, cr.group_sizes(1025))]
+
+
+@pytest.mark.parametrize("H,sizes", HOT_CASES, ids=[f"H{H}-B{len(s)}" for H, s in HOT_CASES])
+def test_hot_regime_leaves_the_linear_range_and_stays_representable(H, sizes):
+    """Conditions on the inputs, not measurements of the kernel: every configuration the GPU tests run "hot"."""
+    W, x, h0 = cr.make_regime("hot", 16, H, 2, 1, 1, sizes)
+    assert not bool(((h0 == 0) | (h0 == 1)).any()) and W["gcl_0.att_mlp.0.weight"].abs().max() > 8 / np.sqrt(H)
+    probe = {}
+    p64 = cr.forward(W, x, h0, sizes, probe=probe)
+    p32 = cr.forward(W, x, h0, sizes, dtype=torch.float32)
+    assert bool(torch.isfinite(p32).all())
+    stds = [float(g.std()) for g in probe["gate"]]
+    beyond = [float((torch.cat((a, b)).abs() > 4).double().mean()) for a, b in zip(probe["pre0"], probe["pre2"])]
+    rel = float((p32.double() - p64).abs().max() / p64.abs().max())
+    print(f"hot H={H}: gate std per layer {stds}, share of edge_mlp pre-activations beyond 4 {beyond}, relative fp32 gap {rel:.2e}")
+    assert len(stds) == 2 and min(stds) >= 0.1
+    assert min(beyond) >= 0.05
+    assert rel < 1e-4
+
+
+def test_init_regime_is_the_near_linear_one():
+    W, x, h0 = cr.make_regime("init", 16, 96, 2, 1, 1, cr.INSTANTIATION_SIZES)
+    assert bool(((h0 == 0) | (h0 == 1)).all()) and all(torch.equal(v, w) for v, w in zip(W.values(), synth.make_weights(
+        cr.state_dict_shapes(16, 96, 2, True, True), seed=11).values()))
+    probe = {}
+    cr.forward(W, x, h0, cr.INSTANTIATION_SIZES, probe=probe)
+    assert max(float(g.std()) for g in probe["gate"]) < 0.05             # why "hot" exists: the gate is one number here
+
+
+def test_size_lists_hold_the_named_pairs_and_edges():
+    assert cr.INSTANTIATION_SIZES == [1, 2, 3, 4, 5, 8, 9, 16, 31, 32, 0, 7]
+    s = cr.group_sizes(1025)
+    assert len(s) == 1025 and len(s) % 2 == 1 and s == cr.group_sizes(1025)
+    pairs = [(s[2 * k], s[2 * k + 1]) for k in range(len(s) // 2)]
+    assert pairs[:7] == [(32, 32), (0, 32), (32, 0), (0, 0), (1, 1), (1, 32), (4, 5)] == cr.GROUP_PAIRS
+    assert set(s) == set(range(33)) and sum(s) <= 32 * len(s)
+    assert cr.offsets_of([3, 0, 2]) == [0, 3, 3, 5]
+
+
+def test_the_bar_is_per_molecule_and_per_row():
+    """A defect confined to the two-atom molecule that the batch-wide bar (20 x the batch's gap) lets through fails the per-molecule bar; the
+    restatement's own fp32 run needs M <= 1; an entry left NaN fails."""
+    sizes = list(range(1, 33))
+    W, x, h0 = cr.make_regime("init", 5, 64, 2, 1, 0, sizes)
+    ref = cr.references(W, x, h0, sizes)
+    assert ref.pred64.dtype == torch.float64 and len(ref.layers64) == 3 and ref.layers32[2].shape == (sum(sizes), 64)
+    assert torch.get_num_threads() >= 1 and bool((ref.pred_scale >= ref.pred64.abs() - 1e-12).all())
+    failures, ratios = cr.compare(ref, pred=ref.pred32, layers=dict(enumerate(ref.layers32)))
+    assert not failures and max(ratios.values()) <= 1.0 and set(ratios) == {"pred", "h0", "h1", "h2"}
+    batch_gap = float((ref.pred32 - ref.pred64).abs().max())
+    wrong = ref.pred32.clone()
+    wrong[1] += 10 * batch_gap                                            # half the batch-wide bar of tests/test_classifier_gpu.py
+    assert float((wrong - ref.pred64).abs().max()) <= 20 * batch_gap
+    failures, ratios = cr.compare(ref, pred=wrong)
+    assert len(failures) == 1 and "molecule 1 " in failures[0] and ratios["pred"] > cr.M_MAX
+    h = ref.layers32[2].clone()
+    h[2, 5] += 20 * float((ref.layers32[2] - ref.layers64[2]).abs()[2].max()) + 1e-5
+    failures, ratios = cr.compare(ref, layers={2: h})
+    assert len(failures) == 1 and "row 2 " in failures[0]
+    h = ref.layers32[0].clone()
+    h[7, 0] = float("nan")
+    failures, ratios = cr.compare(ref, layers={0: h})
+    assert failures and ratios["h0"] == float("inf")
+    assert cr.compare(ref, pred=torch.full_like(ref.pred32, float("nan")))[0]
+    assert set(cr.MARGINS) == {"init", "hot"} and cr.MARGINS["init"] == {}
+    assert all(cr.M_DEFAULT <= m <= cr.M_MAX for reg in cr.MARGINS.values() for m in reg.values())
+
+
 class _StubClassifier:
     """predict() returns a fixed table: property_mae's bookkeeping does not depend on the network."""
 
