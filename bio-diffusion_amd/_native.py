@@ -20,6 +20,7 @@ OPS_LIB_PATH = os.path.join(_HERE, "libgcdm_ops.so")
 OPS_SOURCES = [os.path.join(_HERE, "csrc", "gcdm_ops.hip")]
 OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_ops.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.mp_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_train.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.gcp2.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_gcp2_train.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.classifier.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier.h")]
 ABI_VERSION = 2
@@ -135,6 +136,21 @@ MP_TRAIN_SIGNATURES = {
     "gcdm_mp_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I32, I32, P],
 }
 MP_TRAIN_RESTYPES = {"gcdm_mp_workspace_bytes": C.c_int64}
+
+
+# one stand-alone GCP2 module for training (include/gcdm_gcp2_train.h), exported from the same library
+class Gcp2Dims(C.Structure):
+    _fields_ = [("SI", C.c_int32), ("VI", C.c_int32), ("SO", C.c_int32), ("VO", C.c_int32), ("H", C.c_int32), ("feedforward_out", C.c_int32),
+                ("act_scalar", C.c_int32), ("act_vector", C.c_int32)]
+
+
+GCP2_SIGNATURES = {
+    "gcdm_gcp2_workspace_bytes": [I32, I64, C.POINTER(Gcp2Dims)],
+    "gcdm_gcp2_fwd": [P, P, P, P, P, P, P, P, I32, I64, C.POINTER(Gcp2Dims), P],
+    "gcdm_gcp2_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, I64, C.POINTER(Gcp2Dims), P],
+}
+GCP2_RESTYPES = {"gcdm_gcp2_workspace_bytes": C.c_int64}
+GCP2_MAX = dict(SI=2048, VI=128, SO=1024, VO=64, H=64)          # GCDM_GCP2_MAX_*
 # the fused training update: clipping, AdamW / AMSGrad, EMA (include/gcdm_optim.h), exported from the same library
 D = C.c_double
 OPTIM_SIGNATURES = {
@@ -165,10 +181,10 @@ def load_ops() -> C.CDLL:
     if not os.path.exists(OPS_LIB_PATH):
         raise RuntimeError(f"{OPS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
     lib = C.CDLL(OPS_LIB_PATH)
-    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()):
+    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(GCP2_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = sig
-        fn.restype = {**MP_TRAIN_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES}.get(name, C.c_int)
+        fn.restype = {**MP_TRAIN_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES}.get(name, C.c_int)
     _ops_lib = lib
     return lib
 

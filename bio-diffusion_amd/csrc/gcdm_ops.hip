@@ -1,11 +1,14 @@
 // libgcdm_ops.so -- the module-level operators (forward + backward) behind plug point 3, the non-production configurations and the
-// training objective, the fused message layer for training, the fused training update, and the EGNN property classifier.  One translation unit, independent of libgcdm_hip.so (the fused sampling
-// path); C ABI in include/gcdm_ops.h, include/gcdm_mp_train.h, include/gcdm_optim.h and include/gcdm_classifier.h.
+// training objective, the fused message layer and the fused stand-alone GCP2 for training, the fused training update, and the EGNN property
+// classifier.  One translation unit, independent of libgcdm_hip.so (the fused sampling path); C ABI in include/gcdm_ops.h,
+// include/gcdm_mp_train.h, include/gcdm_gcp2_train.h, include/gcdm_optim.h and include/gcdm_classifier.h.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -o bio-diffusion_amd/libgcdm_ops.so bio-diffusion_amd/csrc/gcdm_ops.hip
 #include "gcdm_ops.hip.h"
 #include "../../include/gcdm_ops.h"
 #include "gcdm_ops.mp_train.hip.h"
 #include "../../include/gcdm_mp_train.h"
+#include "../../include/gcdm_gcp2_train.h"
+#include "gcdm_ops.gcp2.hip.h"
 #include "../../include/gcdm_optim.h"
 #include "gcdm_ops.optim.hip.h"
 #include "../../include/gcdm_classifier.h"

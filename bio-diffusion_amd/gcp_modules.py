@@ -133,6 +133,65 @@ class GCP2(_GCPBase):
         else:
             self.scalar_out = self._make_scalar_out(self.scalar_input_dim, feedforward_out, scalar_out_nonlinearity)
 
+        # Which kernels evaluate forward(): "operators" (default) = the operator graph below, any configuration; "fused" = the whole module as
+        # one autograd node (ops.gcp2_fused), for the configuration why_not_fused() accepts.
+        self.path = "operators"
+
+    def why_not_fused(self) -> Optional[str]:
+        """None if ops.gcp2_fused (include/gcdm_gcp2_train.h) implements this module's configuration, else the first reason it does not."""
+        def act_ok(n):
+            return _is_identity(n) or (isinstance(n, str) and n.lower() in ("silu", "swish"))
+        checks = [
+            (self.vector_input_dim > 0, "no vector inputs (vector_input_dim = 0)"),
+            (not (self.scalar_gate and self.scalar_gate > 0), f"scalar_gate = {self.scalar_gate}"),
+            (not self.frame_gate, "frame_gate"),
+            (not self.sigma_frame_gate, "sigma_frame_gate"),
+            (self.vector_gate, "no vector_gate"),
+            (not self.vector_residual, "vector_residual"),
+            (not self.vector_frame_residual, "vector_frame_residual"),
+            (not self.ablate_frame_updates, "ablate_frame_updates"),
+            (not self.ablate_scalars, "ablate_scalars"),
+            (not self.ablate_vectors, "ablate_vectors"),
+            (self.sv_dim == 3, f"scalarization_vectorization_output_dim = {self.sv_dim}"),
+            (act_ok(self.nonlinearities[0]) and act_ok(self.nonlinearities[1]), f"nonlinearities {self.nonlinearities} (identity or silu)"),
+            (not self.feedforward_out or (isinstance(self._ff_act, str) and self._ff_act.lower() in ("silu", "swish")),
+             f"scalar_out_nonlinearity = {self._ff_act!r}"),
+        ]
+        for ok, why in checks:
+            if not ok:
+                return why
+        return ops.gcp2_why_not_dims(self.scalar_input_dim, self.vector_input_dim, self.scalar_output_dim, self.vector_output_dim, self.hidden_dim)
+
+    def set_path(self, path: str) -> None:
+        if path not in ("operators", "fused"):
+            raise ValueError(f"GCP2.path must be 'operators' or 'fused', got {path!r}")
+        if path == "fused":
+            why = self.why_not_fused()
+            if why is not None:
+                raise NotImplementedError(f"node path 'fused': the fused GCP2 does not implement this configuration ({why})")
+        self.path = path
+
+    def fused_weights(self):
+        """The module's Linear tensors in the order of include/gcdm_gcp2_train.h (state-dict order)."""
+        ws = [self.vector_down.weight, self.vector_down_frames.weight]
+        if self.feedforward_out:
+            ws += [self.scalar_out[0].weight, self.scalar_out[0].bias, self.scalar_out[2].weight, self.scalar_out[2].bias]
+        else:
+            ws += [self.scalar_out.weight, self.scalar_out.bias]
+        if self.vector_output_dim:
+            ws += [self.vector_up.weight, self.vector_out_scale.weight, self.vector_out_scale.bias]
+        return ws
+
+    def _forward_fused(self, s_maybe_v, edge_index, frames, node_inputs, node_mask):
+        why = self.why_not_fused()
+        if why is not None:
+            raise NotImplementedError(f"node path 'fused': the fused GCP2 does not implement this configuration ({why})")
+        s, v = s_maybe_v
+        F = _entity_frames(edge_index, frames, node_inputs, v.shape[0], node_mask)
+        s_out, v_out = ops.gcp2_fused(s, v, F, self.fused_weights(), self.scalar_output_dim, self.vector_output_dim, self.hidden_dim,
+                                      feedforward_out=self.feedforward_out, act_scalar=self.nonlinearities[0], act_vector=self.nonlinearities[1])
+        return (s_out, v_out) if self.vector_output_dim else s_out
+
     def _vector_out(self, s_pre_act: torch.Tensor, v_pre: torch.Tensor, vh: torch.Tensor, F: Optional[torch.Tensor]) -> torch.Tensor:
         """process_vector_with_frames / process_vector_without_frames (:357-408)."""
         up = ops.linear(vh, self.vector_up.weight)                      # [M, 3, V_out]
@@ -152,6 +211,8 @@ class GCP2(_GCPBase):
 
     def forward(self, s_maybe_v, edge_index: torch.Tensor, frames: torch.Tensor, node_inputs: bool = False,
                 node_mask: Optional[torch.Tensor] = None):
+        if self.path == "fused":
+            return self._forward_fused(s_maybe_v, edge_index, frames, node_inputs, node_mask)
         F = None
         if self.vector_input_dim:
             s, v, v_pre = self._inputs(s_maybe_v)

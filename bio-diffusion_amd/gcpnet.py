@@ -148,6 +148,37 @@ class GCPNetDynamics(nn.Module):
         paths = {layer.interaction.path for layer in self.interaction_layers}
         return paths.pop() if len(paths) == 1 else "mixed"
 
+    def standalone_gcps(self):
+        """The stand-alone GCP modules of a forward, in call order: the two embedding GCPs, the feed-forward and position GCPs of every
+        interaction layer, the scalar projection (the message GCPs belong to set_message_path)."""
+        mods = [self.gcp_embedding.edge_embedding, self.gcp_embedding.node_embedding]
+        for layer in self.interaction_layers:
+            mods += list(layer.feedforward_network)
+            if layer.update_node_positions:
+                mods.append(layer.node_position_update_gcp)
+        return mods + [self.scalar_node_projection_gcp]
+
+    def set_node_path(self, path: str) -> None:
+        """"operators" (default) | "fused": how every stand-alone GCP2 runs on the module path (training, and any forward_modules call).
+        "fused" = one autograd node per module on libgcdm_ops.so's fused GCP2 kernels (include/gcdm_gcp2_train.h); raises NotImplementedError
+        naming the first reason when a module is outside what they implement.  Independent of set_message_path."""
+        if path not in ("operators", "fused"):
+            raise ValueError(f"node path must be 'operators' or 'fused', got {path!r}")
+        mods = self.standalone_gcps()
+        if path == "fused":
+            for m in mods:
+                why = "module_cfg.selected_GCP is not GCP2" if type(m) is not GCP2 else m.why_not_fused()
+                if why is not None:
+                    raise NotImplementedError(f"node path 'fused': the fused GCP2 does not implement this configuration ({why})")
+        for m in mods:
+            if type(m) is GCP2:
+                m.set_path(path)
+
+    @property
+    def node_path(self) -> str:
+        paths = {getattr(m, "path", "operators") for m in self.standalone_gcps()}
+        return paths.pop() if len(paths) == 1 else "mixed"
+
     def _dropout_active(self) -> bool:
         return self.training and any(l.gcp_dropout[0].use_gcp_dropout and l.gcp_dropout[0].drop_rate > 0 for l in self.interaction_layers)
 

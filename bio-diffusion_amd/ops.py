@@ -619,3 +619,132 @@ def message_layer(h: torch.Tensor, chi: torch.Tensor, e: torch.Tensor, xi: torch
     record = torch.is_grad_enabled() and any(t.requires_grad for t in (h, chi, e, xi, *weights))
     agg = _MessageLayer.apply(h, chi, e, xi, frames, graph, edge_mask, record, *weights)
     return agg[:, :256], agg[:, 256:].reshape(graph.N, 32, 3)
+
+
+# ---- one stand-alone GCP2 module as one autograd node (include/gcdm_gcp2_train.h) -----------------------------------------------------------
+GCP2_MAX = _native.GCP2_MAX
+_GCP2_ACTS = {None: 0, "none": 0, "identity": 0, "silu": 1, "swish": 1}
+
+
+def gcp2_act_code(name) -> int:
+    """0 identity | 1 silu, the two nonlinearities the fused GCP2 takes; raises ValueError for another one."""
+    key = name.lower() if isinstance(name, str) else name
+    if key not in _GCP2_ACTS:
+        raise ValueError(f"gcp2_fused: nonlinearity {name!r} (identity or silu)")
+    return _GCP2_ACTS[key]
+
+
+def gcp2_why_not_dims(SI: int, VI: int, SO: int, VO: int, H: int) -> Optional[str]:
+    """None if the dims are inside the bounds of include/gcdm_gcp2_train.h, else the first one that is not."""
+    for name, val, lo in (("SI", SI, 1), ("VI", VI, 1), ("SO", SO, 1), ("VO", VO, 0), ("H", H, 1)):
+        if not lo <= int(val) <= GCP2_MAX[name]:
+            return f"{name} = {val} outside [{lo}, {GCP2_MAX[name]}]"
+    return None
+
+
+def _gcp2_dims(SI, VI, SO, VO, H, feedforward_out, act_scalar, act_vector) -> "_native.Gcp2Dims":
+    return _native.Gcp2Dims(int(SI), int(VI), int(SO), int(VO), int(H), int(bool(feedforward_out)), int(act_scalar), int(act_vector))
+
+
+def gcp2_workspace_bytes(which: int, M: int, dims) -> int:
+    n = int(_lib().gcdm_gcp2_workspace_bytes(int(which), int(M), C.byref(dims)))
+    if n < 0:
+        raise ValueError(f"gcdm_gcp2_workspace_bytes({which}, M={M}, dims={[getattr(dims, f) for f, _ in dims._fields_]}): bad argument")
+    return n
+
+
+def _gcp2_weight_shapes(SI, VI, SO, VO, H, ff):
+    K = SI + H + 9
+    want = [(H, VI), (3, VI), (SO, K), (SO,)]
+    if ff:
+        want += [(SO, SO), (SO,)]
+    if VO:
+        want += [(VO, H), (VO, SO), (VO,)]
+    return want
+
+
+class _GCP2Fused(torch.autograd.Function):
+    """GCP2.forward of one stand-alone module: two C calls (gcdm_gcp2_fwd / gcdm_gcp2_bwd).  The tape -- what the backward reads beyond s, v and
+    the weights -- is one workspace tensor held by the context and dropped by the backward; under no_grad the forward writes none."""
+
+    @staticmethod
+    def forward(ctx, s, v, F, row_mask, dims, record, *weights):
+        SI, VI, SO, VO, H, ff, a0, a1 = dims
+        M = int(s.shape[0])
+        _shape(s.dim() == 2 and s.shape[1] == SI, f"gcp2_fused: s {tuple(s.shape)} must be [M, {SI}]")
+        _shape(tuple(v.shape) == (M, VI, 3), f"gcp2_fused: v {tuple(v.shape)} must be [{M}, {VI}, 3]")
+        _shape(F.shape[0] == M and F.numel() == 9 * M, f"gcp2_fused: frames {tuple(F.shape)} for {M} rows")
+        why = gcp2_why_not_dims(SI, VI, SO, VO, H)
+        _shape(why is None, f"gcp2_fused: {why}")
+        want = _gcp2_weight_shapes(SI, VI, SO, VO, H, ff)
+        _shape(len(weights) == len(want), f"gcp2_fused: {len(weights)} weight tensors, expected {len(want)}")
+        for i, (w, shp) in enumerate(zip(weights, want)):
+            _shape(tuple(w.shape) == shp, f"gcp2_fused: weight {i} has shape {tuple(w.shape)}, expected {shp}")
+        for t in (s, v, F, *weights):
+            if t.dtype != torch.float32:
+                raise TypeError(f"gcp2_fused: the fused GCP2 computes in fp32; got a {t.dtype} tensor")
+            _dev(t)
+        ss, vs, fs = s.detach().contiguous(), v.detach().contiguous(), F.detach().reshape(M, 9).contiguous()
+        ws = [w.detach().contiguous() for w in weights]
+        mk = None if row_mask is None else row_mask.reshape(-1).to(torch.uint8).contiguous()
+        _shape(mk is None or mk.numel() == M, "gcp2_fused: row_mask must have one entry per row")
+        cd = _gcp2_dims(SI, VI, SO, VO, H, ff, a0, a1)
+        s_out = torch.empty((M, SO), dtype=torch.float32, device=s.device)
+        v_out = torch.empty((M, VO, 3), dtype=torch.float32, device=s.device)
+        tape = bool(record)                 # (grad mode is off inside forward: the caller says whether a graph is being recorded)
+        ws_t = torch.empty(gcp2_workspace_bytes(int(tape), M, cd) // 4, dtype=torch.float32, device=s.device)
+        wp = (C.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
+        _chk(_lib().gcdm_gcp2_fwd(_p(ss), _p(vs), _p(fs), _p(mk), wp, _p(s_out), _p(v_out) if VO else None, _p(ws_t), int(tape), M, C.byref(cd),
+                                  _st(ss)), "gcdm_gcp2_fwd")
+        ctx.tape = ws_t if tape else None
+        del ws_t
+        ctx.frames, ctx.mask, ctx.cd, ctx.M, ctx.VO = fs, mk, cd, M, VO
+        ctx.save_for_backward(ss, vs, *weights)
+        ctx.ws = ws
+        if not VO:
+            ctx.mark_non_differentiable(v_out)
+        return s_out, v_out
+
+    @staticmethod
+    def backward(ctx, ds_out, dv_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("gcp2_fused (fused node path): double backward (create_graph=True) is not supported; use the operator path")
+        if ctx.tape is None:
+            raise RuntimeError("gcp2_fused: the tape of this forward is gone (a second backward through the same graph is not supported)")
+        saved = ctx.saved_tensors
+        ss, vs = saved[0], saved[1]
+        M, cd, VO = ctx.M, ctx.cd, ctx.VO
+        dev = ss.device
+        gs = _f(ds_out).reshape(M, cd.SO)
+        gv = _f(dv_out).reshape(M, VO, 3) if VO else None
+        alloc = torch.zeros if M == 0 else torch.empty          # no rows: the library writes nothing, the gradients are zero
+        ds = alloc((M, cd.SI), dtype=torch.float32, device=dev)
+        dv = alloc((M, cd.VI, 3), dtype=torch.float32, device=dev)
+        dw = alloc(gcp2_workspace_bytes(3, M, cd) // 4, dtype=torch.float32, device=dev)
+        scratch = torch.empty(gcp2_workspace_bytes(2, M, cd) // 4, dtype=torch.float32, device=dev)
+        wp = (C.c_void_p * len(ctx.ws))(*[w.data_ptr() for w in ctx.ws])
+        _chk(_lib().gcdm_gcp2_bwd(_p(gs), _p(gv), _p(ss), _p(vs), _p(ctx.frames), _p(ctx.mask), wp, _p(ctx.tape), _p(scratch), _p(ds), _p(dv), _p(dw),
+                                  M, C.byref(cd), _st(gs)), "gcdm_gcp2_bwd")
+        ctx.tape = None
+        del scratch
+        grads, o = [], 0
+        for w in ctx.ws:
+            grads.append(dw[o: o + w.numel()].view(w.shape))
+            o += w.numel()
+        ctx.ws = None
+        need = ctx.needs_input_grad
+        return ((ds if need[0] else None), (dv if need[1] else None), None, None, None, None,
+                *[gr if need[6 + i] else None for i, gr in enumerate(grads)])
+
+
+def gcp2_fused(s: torch.Tensor, v: torch.Tensor, F: torch.Tensor, weights, SO: int, VO: int, H: int, feedforward_out: bool = False,
+               act_scalar=None, act_vector=None, row_mask: Optional[torch.Tensor] = None):
+    """One stand-alone GCP2 (vector_gate, no frame gate, no residuals, no ablations) as one autograd node on libgcdm_ops.so's fused kernels.
+    ``s`` [M, SI], ``v`` [M, VI, 3], ``F`` [M, 3, 3] the entity frames (constant: no gradient), ``weights`` the module's Linear tensors in
+    state-dict order (include/gcdm_gcp2_train.h), ``H`` its hidden_dim, the nonlinearities None / "silu"; ``row_mask`` [M]: False zeroes the
+    row's frame.  -> (s_out [M, SO], v_out [M, VO, 3]).  Raises (no fallback) for shapes, dims or dtypes the kernels do not take."""
+    _shape(s.dim() == 2 and v.dim() == 3, f"gcp2_fused: s {tuple(s.shape)} / v {tuple(v.shape)} must be [M, SI] / [M, VI, 3]")
+    dims = (int(s.shape[1]), int(v.shape[1]), int(SO), int(VO), int(H), bool(feedforward_out), gcp2_act_code(act_scalar), gcp2_act_code(act_vector))
+    weights = list(weights)
+    record = torch.is_grad_enabled() and any(t.requires_grad for t in (s, v, *weights))
+    return _GCP2Fused.apply(s, v, F, row_mask, dims, record, *weights)

@@ -1,6 +1,6 @@
 """Where a training step of the module path spends its time (GPU box): wall clock per step against the GPU-side kernel time of the same steps.
 
-    python tools/train_step_probe.py [steps] [--message-path operators|fused]   -> wall ms / step, host enqueue ms / step, HIP-event ms / step
+    python tools/train_step_probe.py [steps] [--message-path operators|fused] [--node-path operators|fused]   -> wall ms / step, host enqueue ms / step, HIP-event ms / step
     rocprofv3 --kernel-trace --stats -- python tools/train_step_probe.py 5      (sum of kernel durations / steps = GPU busy time per step)
 
 --update torch|fused adds the update after backward(): `torch` the reference's recipe in stock torch (adaptive clipping with two host
@@ -8,6 +8,9 @@ syncs, AdamW amsgrad, the per-entry EMA), `fused` optim.TrainingUpdate (three la
 
 --message-path fused runs every interaction layer's message function as one autograd node on the fused message kernels
 (GCPNetDynamics.set_message_path, include/gcdm_mp_train.h); the default is the operator path bench.py times.
+
+--node-path fused runs every stand-alone GCP2 (the embedding GCPs, the feed-forward and position GCPs of each layer, the scalar projection) as
+one autograd node on the fused GCP2 kernels (GCPNetDynamics.set_node_path, include/gcdm_gcp2_train.h); independent of --message-path.
 
 The step is bench.py's `training_step`: forward in training mode + loss + backward of one 64-molecule QM9 batch through libgcdm_ops.so's operators."""
 import importlib
@@ -44,7 +47,7 @@ def _torch_update(params):
     return step
 
 
-def build_step(message_path="operators", update="none"):
+def build_step(message_path="operators", update="none", node_path="operators"):
     import synth
     pkg = importlib.import_module("bio-diffusion_amd")
     dev = torch.device("cuda", 0)
@@ -58,6 +61,7 @@ def build_step(message_path="operators", update="none"):
                 p.mul_(0.25)
     net = net.to(dev)
     net.set_message_path(message_path)
+    net.set_node_path(node_path)
     info = pkg.dataset_info("qm9")
     ddpm = pkg.EquivariantVariationalDiffusion(net, cfgs["diffusion_cfg"], cfgs["dataloader_cfg"], info).to(dev)
     ddpm._native(dev)
@@ -96,10 +100,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("steps", nargs="?", type=int, default=10)
     ap.add_argument("--message-path", choices=("operators", "fused"), default="operators")
+    ap.add_argument("--node-path", choices=("operators", "fused"), default="operators")
     ap.add_argument("--update", choices=("none", "torch", "fused"), default="none")
     args = ap.parse_args()
     steps = args.steps
-    once, dev = build_step(args.message_path, args.update)
+    once, dev = build_step(args.message_path, args.update, args.node_path)
     for _ in range(3):
         once()
     torch.cuda.synchronize(dev)
@@ -112,7 +117,7 @@ def main():
     t_host = (time.perf_counter() - t0) / steps * 1e3          # host done enqueueing
     torch.cuda.synchronize(dev)
     wall = (time.perf_counter() - t0) / steps * 1e3
-    print(f"training step, 64 x 19, message path {args.message_path}, update {args.update}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
+    print(f"training step, 64 x 19, message path {args.message_path}, node path {args.node_path}, update {args.update}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
 
 
 if __name__ == "__main__":
