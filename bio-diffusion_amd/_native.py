@@ -18,7 +18,7 @@ HEADERS = ([os.path.join(_HERE, "csrc", f) for f in sorted(os.listdir(os.path.jo
 # the module-level operators (forward + backward) live in their own small library (include/gcdm_ops.h)
 OPS_LIB_PATH = os.path.join(_HERE, "libgcdm_ops.so")
 OPS_SOURCES = [os.path.join(_HERE, "csrc", "gcdm_ops.hip")]
-OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_ops.h"),
+OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(_HERE, "csrc", "gcdm_ops.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_ops.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.mp_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_train.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.gcp2.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_gcp2_train.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h"),

@@ -1,36 +1,32 @@
 // gcdm_ops.gcp2.hip.h -- one stand-alone GCP2 module (GCP2.forward, reference gcpnet.py:418-491 + process_vector_with_frames :378-415) as one
 // training operator, forward and backward: the embedding GCPs, the feed-forward GCP and the position GCP of an interaction layer, the scalar
-// projection.  C ABI: include/gcdm_gcp2_train.h.  Exact fp32 (every GEMM on v_mfma_f32_32x32x2_f32, the tile body is gops::k_gemm's); no float
-// atomics; a row's results depend on that row alone (the MFMA accumulates each row over k in a fixed order), so they are the same bits whatever
-// M is.
+// projection.  C ABI: include/gcdm_gcp2_train.h.  Exact fp32 (every GEMM on gops::tile_mma, gcdm_ops.tile.hip.h, its A operand computed on
+// load where the kernels below say so); no float atomics; a row's results depend on that row alone (the MFMA accumulates each row over k in a
+// fixed order), so they are the same bits whatever M is.
 //
 // Forward, 2 launches (3 with feedforward_out):
 //   k_gcp2_down     one wave per row: vh = vector_down(v), X = [s | |vh| | q] (q: the frame scalars of vector_down_frames(v)), and
 //                   vector_up(vh) written straight into v_out;
-//   (gops::k_gemm   hid = X W0^T + b0 when feedforward_out;)
+//   (gops::gemm     hid = X W0^T + b0 when feedforward_out;)
 //   k_gcp2_scalar   one workgroup per 64 rows, all SO columns in 64-wide tiles: p = A W^T + b (A = X, or silu(hid) applied on load), s_out =
 //                   act0(p); act1(p) goes through LDS into the gate GEMM of the same rows, whose epilogue scales v_out by sigmoid(gate).
 // Backward, 5 launches (6 with feedforward_out):
 //   k_gcp2_gate_bwd dp = ds_out act0'(p) + (dgate W_g) act1'(p); the A operand dgate is computed on load (vector_up and the sigmoid are
 //                   recomputed from vh and the gate pre-activation), dup / dgate are kept for the weight gradients;
 //   (k_gcp2_ff_bwd  dhid = (dp W2) silu'(hid) when feedforward_out;)
-//   gops::k_gemm    dX = dp W_s (dhid W0);
+//   gops::gemm      dX = dp W_s (dhid W0);
 //   k_gcp2_down_bwd one wave per row: norms, frame scalars and the two down projections -> ds, dv, and dvh / du / v in the "pre" layout for
-//   gmp::k_mp_wgrad + gops::k_reduce_slices: every weight gradient, biases included, in one grouped split-K launch and one slice reduction.
+//   gops::wgrad_launch: every weight gradient, biases included, in one grouped split-K launch and one slice reduction.
 #pragma once
 
 namespace ggcp {
 
-using gops::f32x16;
-using gops::GK;
-using gops::GM;
-using gops::GN;
+using namespace gops;
 
 struct Dims {
     int64_t M;
     int SI, VI, SO, VO, H, K, ff, a0, a1;
 };
-inline int64_t a4(int64_t n) { return (n + 63) & ~(int64_t)63; }        // 256-byte aligned float counts
 
 // positions in the weight table (include/gcdm_gcp2_train.h)
 struct WIdx {
@@ -67,14 +63,13 @@ struct FwdLayout {
 };
 inline FwdLayout fwd_layout(const Dims& d, int tape) {
     FwdLayout L;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t r = o; o += a4(n); return r; };
-    L.x = take(d.M * d.K);
-    L.hid = d.ff ? take(d.M * d.SO) : -1;
-    L.vh = tape ? take(d.M * 3 * d.H) : -1;
-    L.p = tape ? take(d.M * d.SO) : -1;
-    L.gate = (tape && d.VO) ? take(d.M * d.VO) : -1;
-    L.total = o;
+    Arena ar;
+    L.x = ar.take(d.M * d.K);
+    L.hid = d.ff ? ar.take(d.M * d.SO) : -1;
+    L.vh = tape ? ar.take(d.M * 3 * d.H) : -1;
+    L.p = tape ? ar.take(d.M * d.SO) : -1;
+    L.gate = (tape && d.VO) ? ar.take(d.M * d.VO) : -1;
+    L.total = ar.o;
     return L;
 }
 struct BwdLayout {
@@ -82,94 +77,33 @@ struct BwdLayout {
 };
 inline BwdLayout bwd_layout(const Dims& d) {
     BwdLayout L;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t r = o; o += a4(n); return r; };
-    L.one = take(1);                         // 1.0f: the B operand of the bias gradients (stride 0)
-    L.vpre = take(d.M * 3 * d.VI);           // v in the "pre" layout [M][3][VI]
-    L.dvh = take(d.M * 3 * d.H);
-    L.du = take(d.M * 9);
-    L.dup = d.VO ? take(d.M * 3 * d.VO) : -1;
-    L.dgate = d.VO ? take(d.M * d.VO) : -1;
-    L.dp = take(d.M * d.SO);
-    L.ga = d.VO ? take(d.M * d.SO) : -1;     // act1(p): the input of the gate GEMM, recomputed
-    L.dhid = d.ff ? take(d.M * d.SO) : -1;
-    L.a2 = d.ff ? take(d.M * d.SO) : -1;     // silu(hid), recomputed
-    L.dx = take(d.M * d.K);
-    L.part = take((int64_t)gmp::WG_SLICES * weight_total(d));
-    L.total = o;
+    Arena ar;
+    L.one = ar.take(1);                         // 1.0f: the B operand of the bias gradients (stride 0)
+    L.vpre = ar.take(d.M * 3 * d.VI);           // v in the "pre" layout [M][3][VI]
+    L.dvh = ar.take(d.M * 3 * d.H);
+    L.du = ar.take(d.M * 9);
+    L.dup = d.VO ? ar.take(d.M * 3 * d.VO) : -1;
+    L.dgate = d.VO ? ar.take(d.M * d.VO) : -1;
+    L.dp = ar.take(d.M * d.SO);
+    L.ga = d.VO ? ar.take(d.M * d.SO) : -1;     // act1(p): the input of the gate GEMM, recomputed
+    L.dhid = d.ff ? ar.take(d.M * d.SO) : -1;
+    L.a2 = d.ff ? ar.take(d.M * d.SO) : -1;     // silu(hid), recomputed
+    L.dx = ar.take(d.M * d.K);
+    L.part = ar.take((int64_t)WG_SLICES * weight_total(d));
+    L.total = ar.o;
     return L;
 }
 
-__device__ __forceinline__ float act_f(int silu, float x) { return silu ? x / (1.f + expf(-x)) : x; }
-__device__ __forceinline__ float act_df(int silu, float x) {
-    if (!silu) return 1.f;
-    const float s = 1.f / (1.f + expf(-x));
-    return s * (1.f + x * (1.f - s));
-}
-__device__ __forceinline__ float sigm_f(float x) { return 1.f / (1.f + expf(-x)); }
+// the module's activation flags (Dims a0, a1: silu or none) as a gops::ACT_* kind; the two-way choice stays visible to the compiler
+__device__ __forceinline__ int act_kind(int silu) { return silu ? ACT_SILU : ACT_NONE; }
 
-// ---- one 64 x 64 tile of A[M,K] . B[K,N] over the whole K: gops::k_gemm's body with the A element produced by a functor (row, k) -------------
-// A is addressed k-fast (row-major rows); each element of a K step is produced by exactly one thread, once.  All threads of the workgroup
-// call it together; on return nobody reads As / Bs any more.
-template <class ALoad>
-__device__ __forceinline__ f32x16 tile_mma(const ALoad& aload, const float* __restrict__ B, int64_t sbk, int64_t sbn, int64_t m0, int n0, int64_t M, int N,
-                                           int64_t K, float (*As)[GK][GM + 1], float (*Bs)[GK][GN + 1]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const bool b_nfast = sbn == 1;
-    int am[4], ak[4], bn[4], bk[4];
-    const float* pb[4];
-    bool va[4], vb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = tid + 256 * i;
-        am[i] = idx / GK; ak[i] = idx % GK;
-        bn[i] = b_nfast ? idx % GN : idx / GK; bk[i] = b_nfast ? idx / GN : idx % GK;
-        va[i] = m0 + am[i] < M; vb[i] = n0 + bn[i] < N;
-        pb[i] = B + bk[i] * sbk + (vb[i] ? (int64_t)(n0 + bn[i]) * sbn : 0);
-    }
-    const int64_t db_ = GK * sbk;
-    float ra[4], rb[4];
-    auto fetch = [&](int64_t k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ra[i] = (va[i] && k0 + ak[i] < K) ? aload(m0 + am[i], k0 + ak[i]) : 0.f;
-            rb[i] = (vb[i] && k0 + bk[i] < K) ? *pb[i] : 0.f;
-            pb[i] += db_;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { As[buf][ak[i]][am[i]] = ra[i]; Bs[buf][bk[i]][bn[i]] = rb[i]; }
-    };
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t k0 = 0; k0 < K; k0 += GK) {
-        const bool more = k0 + GK < K;
-        if (more) fetch(k0 + GK);
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2) {
-            const float a = As[buf][kk + (lane >> 5)][wm * 32 + (lane & 31)];
-            const float b = Bs[buf][kk + (lane >> 5)][wn * 32 + (lane & 31)];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
-        if (more) stash(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-    return acc;
-}
-
+// ---- A operands computed on load (gops::FunctorA) ------------------------------------------------------------------------------------------------
 template <int SILU>
 struct RowMajorA {
     const float* A;
     int64_t lda;
     __device__ __forceinline__ float operator()(int64_t r, int64_t k) const {
-        const float x = A[r * lda + k];
-        return SILU ? x / (1.f + expf(-x)) : x;
+        return act_f(act_kind(SILU), A[r * lda + k]);
     }
 };
 
@@ -241,24 +175,24 @@ __global__ __launch_bounds__(256) void k_gcp2_scalar(Dims d, const float* __rest
     const int wm = wave & 1, wn = wave >> 1;
     const int64_t m0 = (int64_t)blockIdx.x * GM;
     const int cl = wn * 32 + (lane & 31);                  // this lane's column inside a tile (of p, and of the gate)
-    const RowMajorA<ASILU> aload{A, Kd};
+    const FunctorA<RowMajorA<ASILU>> aload{{A, Kd}};
     f32x16 gacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int n0 = 0; n0 < d.SO; n0 += GN) {
-        const f32x16 acc = tile_mma(aload, W, 1, Kd, m0, n0, d.M, d.SO, Kd, As, Bs);
+        const f32x16 acc = tile_mma(aload, W, 1, Kd, m0, n0, d.M, d.SO, 0, Kd, As, Bs);
         const int col = n0 + cl;
         const bool cv = col < d.SO;
         const float bv = cv ? bias[col] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rl = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int rl = tile_row(wm, lane, r);
             const int64_t row = m0 + rl;
             const bool ok = cv && row < d.M;
             const float pv = acc[r] + bv;
             if (ok) {
                 if (p_out) p_out[row * d.SO + col] = pv;
-                s_out[row * d.SO + col] = act_f(d.a0, pv);
+                s_out[row * d.SO + col] = act_f(act_kind(d.a0), pv);
             }
-            if (d.VO) Ps[cl][rl] = ok ? act_f(d.a1, pv) : 0.f;
+            if (d.VO) Ps[cl][rl] = ok ? act_f(act_kind(d.a1), pv) : 0.f;
         }
         if (d.VO) {
             __syncthreads();
@@ -278,7 +212,7 @@ __global__ __launch_bounds__(256) void k_gcp2_scalar(Dims d, const float* __rest
         const float bgv = bg[cl];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int64_t row = m0 + tile_row(wm, lane, r);
             if (row < d.M) {
                 const float g = gacc[r] + bgv;
                 if (gate_out) gate_out[row * d.VO + cl] = g;
@@ -329,20 +263,20 @@ __global__ __launch_bounds__(256) void k_gcp2_gate_bwd(Dims d, const float* __re
     const int64_t m0 = (int64_t)blockIdx.x * GM;
     const int n0 = blockIdx.y * GN;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *one = 1.f;
-    const DgateA aload{vh, wup, gate, dv_out, dup, dgate, d.H, d.VO, blockIdx.y == 0};
-    const f32x16 acc = tile_mma(aload, Wg, d.SO, 1, m0, n0, d.M, d.SO, (int64_t)d.VO, As, Bs);      // B(k = c, n) = W_g[c][n]
+    const FunctorA<DgateA> aload{{vh, wup, gate, dv_out, dup, dgate, d.H, d.VO, blockIdx.y == 0}};
+    const f32x16 acc = tile_mma(aload, Wg, d.SO, 1, m0, n0, d.M, d.SO, 0, d.VO, As, Bs);      // B(k = c, n) = W_g[c][n]
     const int col = n0 + wn * 32 + (lane & 31);
     if (col >= d.SO) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int64_t row = m0 + tile_row(wm, lane, r);
         if (row < d.M) {
             const int64_t i = row * d.SO + col;
             const float pv = p[i];
-            float g = ds_out[i] * act_df(d.a0, pv);
+            float g = ds_out[i] * act_df(act_kind(d.a0), pv);
             if (d.VO) {
-                g += acc[r] * act_df(d.a1, pv);
-                ga[i] = act_f(d.a1, pv);
+                g += acc[r] * act_df(act_kind(d.a1), pv);
+                ga[i] = act_f(act_kind(d.a1), pv);
             }
             dp[i] = g;
         }
@@ -358,18 +292,18 @@ __global__ __launch_bounds__(256) void k_gcp2_ff_bwd(Dims d, const float* __rest
     const int wm = wave & 1, wn = wave >> 1;
     const int64_t m0 = (int64_t)blockIdx.x * GM;
     const int n0 = blockIdx.y * GN;
-    const RowMajorA<0> aload{dp, d.SO};
-    const f32x16 acc = tile_mma(aload, W2, d.SO, 1, m0, n0, d.M, d.SO, (int64_t)d.SO, As, Bs);       // B(k, n) = W2[k][n]
+    const FunctorA<RowMajorA<0>> aload{{dp, d.SO}};
+    const f32x16 acc = tile_mma(aload, W2, d.SO, 1, m0, n0, d.M, d.SO, 0, d.SO, As, Bs);       // B(k, n) = W2[k][n]
     const int col = n0 + wn * 32 + (lane & 31);
     if (col >= d.SO) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int64_t row = m0 + tile_row(wm, lane, r);
         if (row < d.M) {
             const int64_t i = row * d.SO + col;
             const float hv = hid[i];
-            dhid[i] = acc[r] * act_df(1, hv);
-            a2[i] = act_f(1, hv);
+            dhid[i] = acc[r] * act_df(ACT_SILU, hv);
+            a2[i] = act_f(ACT_SILU, hv);
         }
     }
 }
@@ -497,7 +431,7 @@ int gcdm_gcp2_fwd(const float* s, const float* v, const float* F, const uint8_t*
     const dim3 rows((unsigned)((M + GM - 1) / GM));
     if (d.ff) {
         float* hid = ws + L.hid;
-        gmp_gemm(X, d.K, 1, W[wi.ws], 1, d.K, hid, W[wi.bs], M, d.SO, d.K, st);                         // hid = X W0^T + b0
+        gemm(X, d.K, 1, W[wi.ws], 1, d.K, hid, W[wi.bs], M, d.SO, d.K, st);                         // hid = X W0^T + b0
         hipLaunchKernelGGL(k_gcp2_scalar<1>, rows, dim3(256), 0, st, d, (const float*)hid, (int64_t)d.SO, W[wi.w2], W[wi.b2], wg, bg, p, s_out, gate, v_out);
     } else {
         hipLaunchKernelGGL(k_gcp2_scalar<0>, rows, dim3(256), 0, st, d, (const float*)X, (int64_t)d.K, W[wi.ws], W[wi.bs], wg, bg, p, s_out, gate, v_out);
@@ -534,39 +468,31 @@ int gcdm_gcp2_bwd(const float* ds_out, const float* dv_out, const float* s, cons
         hipLaunchKernelGGL(k_gcp2_ff_bwd, tiles, dim3(256), 0, st, d, (const float*)(ws + L.dp), W[wi.w2], t + T.hid, ws + L.dhid, ws + L.a2);
         dpre = ws + L.dhid;
     }
-    gmp_gemm(dpre, d.SO, 1, W[wi.ws], d.K, 1, ws + L.dx, nullptr, M, d.K, d.SO, st);                       // dX = dpre . W_s
+    gemm(dpre, d.SO, 1, W[wi.ws], d.K, 1, ws + L.dx, nullptr, M, d.K, d.SO, st);                       // dX = dpre . W_s
     hipLaunchKernelGGL(k_gcp2_down_bwd, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, d, (const float*)(ws + L.dx), (const float*)dup, vh, v, wup,
                        W[wi.wd], W[wi.wdf], F, row_mask, ws + L.dvh, ws + L.du, ws + L.vpre, ds, dv);
 
     // every weight gradient of the module: one grouped split-K launch, one fixed-order slice reduction
     int64_t sz[MAXW], off[MAXW];
     weight_sizes(d, sz);
-    off[0] = 0;
-    for (int i = 1; i < wi.n; ++i) off[i] = off[i - 1] + sz[i - 1];
-    gmp::WgTable G;
-    G.n = 0; G.tiles = 0; G.total = weight_total(d);
-    auto add = [&](const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, int Mg, int Ng, int64_t K, int64_t o, int ldc) {
-        gmp::WgDesc& g = G.g[G.n++];
-        g.A = A; g.B = B; g.sam = sam; g.sak = sak; g.sbk = sbk; g.sbn = sbn; g.K = K; g.off = o; g.M = Mg; g.N = Ng; g.ldc = ldc; g.tile0 = G.tiles;
-        G.tiles += ((Mg + GM - 1) / GM) * ((Ng + GN - 1) / GN);
-    };
+    WgTable G;
+    G.total = wgrad_offsets(sz, wi.n, off);
     const float* one = ws + L.one;
     const float* vpre = ws + L.vpre;
-    add(ws + L.dvh, 1, d.H, vpre, d.VI, 1, d.H, d.VI, 3 * M, off[wi.wd], d.VI);                            // dW_down = sum_(m,x) dvh^T v_pre
-    add(ws + L.du, 1, 3, vpre, d.VI, 1, 3, d.VI, 3 * M, off[wi.wdf], d.VI);                                // dW_down_frames
-    add(dpre, 1, d.SO, t + T.x, d.K, 1, d.SO, d.K, M, off[wi.ws], d.K);                                    // dW_s = dpre^T X
-    add(dpre, 1, d.SO, one, 0, 0, d.SO, 1, M, off[wi.bs], 1);
+    G.add(ws + L.dvh, 1, d.H, vpre, d.VI, 1, d.H, d.VI, 3 * M, off[wi.wd], d.VI);                            // dW_down = sum_(m,x) dvh^T v_pre
+    G.add(ws + L.du, 1, 3, vpre, d.VI, 1, 3, d.VI, 3 * M, off[wi.wdf], d.VI);                                // dW_down_frames
+    G.add(dpre, 1, d.SO, t + T.x, d.K, 1, d.SO, d.K, M, off[wi.ws], d.K);                                    // dW_s = dpre^T X
+    G.add(dpre, 1, d.SO, one, 0, 0, d.SO, 1, M, off[wi.bs], 1);
     if (d.ff) {
-        add(ws + L.dp, 1, d.SO, ws + L.a2, d.SO, 1, d.SO, d.SO, M, off[wi.w2], d.SO);                      // dW_2 = dp^T silu(hid)
-        add(ws + L.dp, 1, d.SO, one, 0, 0, d.SO, 1, M, off[wi.b2], 1);
+        G.add(ws + L.dp, 1, d.SO, ws + L.a2, d.SO, 1, d.SO, d.SO, M, off[wi.w2], d.SO);                      // dW_2 = dp^T silu(hid)
+        G.add(ws + L.dp, 1, d.SO, one, 0, 0, d.SO, 1, M, off[wi.b2], 1);
     }
     if (d.VO) {
-        add(dup, 1, d.VO, vh, d.H, 1, d.VO, d.H, 3 * M, off[wi.wup], d.H);                                 // dW_up = sum dup^T vh
-        add(dgate, 1, d.VO, ga, d.SO, 1, d.VO, d.SO, M, off[wi.wg], d.SO);                                 // dW_gate = dgate^T act1(p)
-        add(dgate, 1, d.VO, one, 0, 0, d.VO, 1, M, off[wi.bg], 1);
+        G.add(dup, 1, d.VO, vh, d.H, 1, d.VO, d.H, 3 * M, off[wi.wup], d.H);                                 // dW_up = sum dup^T vh
+        G.add(dgate, 1, d.VO, ga, d.SO, 1, d.VO, d.SO, M, off[wi.wg], d.SO);                                 // dW_gate = dgate^T act1(p)
+        G.add(dgate, 1, d.VO, one, 0, 0, d.VO, 1, M, off[wi.bg], 1);
     }
-    hipLaunchKernelGGL(gmp::k_mp_wgrad, dim3((unsigned)G.tiles, 1, gmp::WG_SLICES), dim3(256), 0, st, G, ws + L.part);
-    hipLaunchKernelGGL(gops::k_reduce_slices, dim3(gops_blocks(G.total)), dim3(256), 0, st, ws + L.part, dweights, G.total, (int)gmp::WG_SLICES);
+    wgrad_launch(G, ws + L.part, dweights, st);
     return GOPS_LAUNCH_OK();
 }
 

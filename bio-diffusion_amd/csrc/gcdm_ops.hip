@@ -1,8 +1,11 @@
 // libgcdm_ops.so -- the module-level operators (forward + backward) behind plug point 3, the non-production configurations and the
 // training objective, the fused message layer and the fused stand-alone GCP2 for training, the fused training update, and the EGNN property
 // classifier.  One translation unit, independent of libgcdm_hip.so (the fused sampling path); C ABI in include/gcdm_ops.h,
-// include/gcdm_mp_train.h, include/gcdm_gcp2_train.h, include/gcdm_optim.h and include/gcdm_classifier.h.
+// include/gcdm_mp_train.h, include/gcdm_gcp2_train.h, include/gcdm_optim.h and include/gcdm_classifier.h.  gcdm_ops.tile.hip.h comes first:
+// the MFMA tile body, the GEMM launches and the helpers the operator headers share; those depend on it and on gcdm_ops.hip.h's status
+// macros, not on each other.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -o bio-diffusion_amd/libgcdm_ops.so bio-diffusion_amd/csrc/gcdm_ops.hip
+#include "gcdm_ops.tile.hip.h"
 #include "gcdm_ops.hip.h"
 #include "../../include/gcdm_ops.h"
 #include "gcdm_ops.mp_train.hip.h"

@@ -13,98 +13,9 @@
 // Layouts: scalars [M][C] row-major; vectors in the reference's two layouts, "rep" [M][C][3] and "pre" [M][3][C] (its transpose(-1,-2));
 // frames [M][9] = rows a, b, c of f_ij.  All fp32.  No fallback: a launch failure is reported through the int status.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "gcdm_ops.tile.hip.h"
 
 namespace gops {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// ---- C[M,N] = A[M,K] . B[K,N] (+ bias[N]) on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulate) ---------------------------
-// General strides, so one kernel serves y = x W^T (A = x, B = W^T), dx = dy W (A = dy, B = W) and dW = dy^T x (A = dy^T, B = x).
-// 64 x 64 tile per 256-thread workgroup (4 waves, 32 x 32 each), K in steps of 16 through LDS; grid.z = split-K slices writing
-// C + z * M * N (reduced in fixed order by k_reduce_slices: deterministic).
-constexpr int GM = 64, GN = 64, GK = 16;
-
-// Round 3: the per-thread element addresses are set up once (pointer += stride per K step instead of two 64-bit multiplies per element and
-// step), the next K step's 8 elements are requested into registers before the current step's MFMAs and stored into the OTHER half of a
-// double-buffered LDS tile behind them -- one barrier per step, global latency under the MFMAs.
-__global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, int64_t sam, int64_t sak, const float* __restrict__ B, int64_t sbk,
-                                              int64_t sbn, float* __restrict__ C, const float* __restrict__ bias, int64_t M, int N, int64_t K,
-                                              int64_t kslice) {
-    __shared__ float As[2][GK][GM + 1];
-    __shared__ float Bs[2][GK][GN + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int64_t m0 = (int64_t)blockIdx.x * GM;
-    const int n0 = blockIdx.y * GN;
-    const int64_t k_begin = (int64_t)blockIdx.z * kslice, k_end = k_begin + kslice < K ? k_begin + kslice : K;
-    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const bool a_kfast = sak == 1, b_nfast = sbn == 1;
-    // this thread's 4 + 4 elements of a K step: tile coordinates, running global pointers, row / column validity
-    int am[4], ak[4], bn[4], bk[4];
-    const float* pa[4];
-    const float* pb[4];
-    bool va[4], vb[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = tid + 256 * i;
-        am[i] = a_kfast ? idx / GK : idx % GM; ak[i] = a_kfast ? idx % GK : idx / GM;
-        bn[i] = b_nfast ? idx % GN : idx / GK; bk[i] = b_nfast ? idx / GN : idx % GK;
-        va[i] = m0 + am[i] < M; vb[i] = n0 + bn[i] < N;
-        pa[i] = A + (va[i] ? (m0 + am[i]) * sam : 0) + (k_begin + ak[i]) * sak;
-        pb[i] = B + (k_begin + bk[i]) * sbk + (vb[i] ? (int64_t)(n0 + bn[i]) * sbn : 0);
-    }
-    const int64_t da = GK * sak, db_ = GK * sbk;
-    float ra[4], rb[4];
-    auto fetch = [&](int64_t k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ra[i] = (va[i] && k0 + ak[i] < k_end) ? *pa[i] : 0.f;
-            rb[i] = (vb[i] && k0 + bk[i] < k_end) ? *pb[i] : 0.f;
-            pa[i] += da; pb[i] += db_;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { As[buf][ak[i]][am[i]] = ra[i]; Bs[buf][bk[i]][bn[i]] = rb[i]; }
-    };
-    fetch(k_begin);
-    stash(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t k0 = k_begin; k0 < k_end; k0 += GK) {
-        const bool more = k0 + GK < k_end;
-        if (more) fetch(k0 + GK);                     // in flight during the MFMAs below
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2) {
-            const float a = As[buf][kk + (lane >> 5)][wm * 32 + (lane & 31)];
-            const float b = Bs[buf][kk + (lane >> 5)][wn * 32 + (lane & 31)];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
-        if (more) stash(buf ^ 1);                     // the other half: nobody reads it before the barrier
-        __syncthreads();
-        buf ^= 1;
-    }
-    float* Cz = C + (int64_t)blockIdx.z * M * N;
-    const int col = n0 + wn * 32 + (lane & 31);
-    if (col < N) {
-        const float bv = (bias && blockIdx.z == 0) ? bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (row < M) Cz[row * N + col] = acc[r] + bv;
-        }
-    }
-}
-
-__global__ void k_reduce_slices(const float* __restrict__ part, float* __restrict__ out, int64_t n, int slices) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = 0.f;
-    for (int z = 0; z < slices; ++z) s += part[(int64_t)z * n + i];
-    out[i] = s;
-}
 
 // column sums of dy [M][N] (bias gradient): one workgroup per 64 columns, fixed summation order (rows strided over the threads, then a tree)
 __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ dy, float* __restrict__ db, int64_t M, int N) {
@@ -132,31 +43,7 @@ __global__ __launch_bounds__(256) void k_colsum_slices(const float* __restrict__
     if (g == 0 && c < N) part[(int64_t)blockIdx.y * N + c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-// ---- element-wise nonlinearities (get_nonlinearity, components/__init__.py: relu / leakyrelu / selu / silu; + sigmoid) --------------------
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_LEAKYRELU = 4, ACT_SELU = 5 };
-// expf / expm1f, not __expf: the fast exp2-based form loses relative accuracy at large negative x (SiLU, sigmoid) and `__expf(x) - 1`
-// cancels completely near 0- (SELU); the kernels are memory-bound, the accurate forms cost nothing measurable.  ReLU keeps NaN (x < 0 is
-// false for it), as torch.relu does.
-__device__ __forceinline__ float act_f(int kind, float x) {
-    switch (kind) {
-        case ACT_SILU: return x / (1.f + expf(-x));
-        case ACT_RELU: return x < 0.f ? 0.f : x;
-        case ACT_SIGMOID: return 1.f / (1.f + expf(-x));
-        case ACT_LEAKYRELU: return x > 0.f ? x : 0.01f * x;
-        case ACT_SELU: return 1.0507009873554804934193349852946f * (x > 0.f ? x : 1.6732632423543772848170429916717f * expm1f(x));
-        default: return x;
-    }
-}
-__device__ __forceinline__ float act_df(int kind, float x) {
-    switch (kind) {
-        case ACT_SILU: { const float s = 1.f / (1.f + expf(-x)); return s * (1.f + x * (1.f - s)); }
-        case ACT_RELU: return x > 0.f ? 1.f : 0.f;
-        case ACT_SIGMOID: { const float s = 1.f / (1.f + expf(-x)); return s * (1.f - s); }
-        case ACT_LEAKYRELU: return x > 0.f ? 1.f : 0.01f;
-        case ACT_SELU: return 1.0507009873554804934193349852946f * (x > 0.f ? 1.f : 1.6732632423543772848170429916717f * expf(x));
-        default: return 1.f;
-    }
-}
+// ---- element-wise nonlinearities (act_f / act_df: gcdm_ops.tile.hip.h) -----------------------------------------------------------------------
 __global__ void k_act(int kind, const float* __restrict__ x, float* __restrict__ y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = act_f(kind, x[i]);
@@ -401,9 +288,7 @@ int gcdm_op_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64
     GOPS_REQUIRE(M >= 0 && N >= 0 && K >= 0 && slices >= 1);
     if (M == 0 || N == 0) return 0;
     GOPS_REQUIRE(A && B && C);
-    const int64_t kslice = ((K + slices - 1) / slices + gops::GK - 1) / gops::GK * gops::GK;
-    const dim3 grid((unsigned)((M + gops::GM - 1) / gops::GM), (unsigned)((N + gops::GN - 1) / gops::GN), (unsigned)slices);
-    hipLaunchKernelGGL(gops::k_gemm, grid, dim3(256), 0, (hipStream_t)stream, A, sam, sak, B, sbk, sbn, C, bias, M, N, K, kslice > 0 ? kslice : gops::GK);
+    gops::gemm(A, sam, sak, B, sbk, sbn, C, bias, M, N, K, (hipStream_t)stream, slices);
     return GOPS_LAUNCH_OK();
 }
 int gcdm_op_reduce_slices(const float* part, float* out, int64_t n, int32_t slices, void* stream) {

@@ -1,7 +1,8 @@
 // gcdm_ops.mp_train.hip.h -- the message function of one interaction layer (GCPMessagePassing.forward, reference gcpnet.py:676-737) as one
 // training operator, forward and backward, for the configuration the fused sampling kernels take at the message layer: GCP2 with vector_gate,
 // silu / silu, bottleneck 4, four residual message GCPs, scalar attention, sum aggregation, node dims (256, 32), edge dims (SE, VE) in
-// {(64, 16), (16, 8)}.  C ABI: include/gcdm_mp_train.h.  Exact fp32 throughout (the GEMMs are gops::k_gemm on v_mfma_f32_32x32x2_f32);
+// {(64, 16), (16, 8)}.  C ABI: include/gcdm_mp_train.h.  Exact fp32 throughout (every GEMM is gops::gemm, every weight gradient one
+// gops::wgrad_launch: gcdm_ops.tile.hip.h);
 // no float atomics: every sum over edges runs in a fixed order, so two backward passes give the same bits.
 //
 // msg0 column split: W_s [h_i | e | h_j | |vh| | q] = W_i h_i + W_j h_j + W_r [e | |vh| | q] + b.  The node halves are one
@@ -13,6 +14,8 @@
 #pragma once
 
 namespace gmp {
+
+using namespace gops;
 
 constexpr int S = 256, V = 32, H = 8, SV = 3, KX = S + H + 3 * SV;       // message state width, vector channels, hidden of msg1-3, X width
 constexpr int NW = 30;                                                 // weight tensors of the layer (include/gcdm_mp_train.h)
@@ -27,7 +30,6 @@ __host__ __device__ inline Dims make_dims(int64_t N, int64_t E, int SE, int VE) 
     d.VIN0 = 2 * V + VE; d.H0 = d.VIN0 / 4; d.K0 = SE + d.H0 + 3 * SV; d.KIN0 = 2 * S + d.K0;
     return d;
 }
-inline int64_t a4(int64_t n) { return (n + 63) & ~(int64_t)63; }        // 256-byte aligned float counts
 
 // Workspace of gcdm_mp_fwd (tape = 1: everything the backward reads; tape = 0: the same buffers shared across the four GCPs) and of
 // gcdm_mp_bwd.  Offsets in floats.
@@ -36,24 +38,23 @@ struct FwdLayout {
 };
 inline FwdLayout fwd_layout(const Dims& d, int tape) {
     FwdLayout L;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t r = o; o += a4(n); return r; };
+    Arena ar;
     const int64_t E = d.E;
-    L.wij = take((int64_t)2 * S * S);
-    L.wr0 = take((int64_t)S * d.K0);
-    L.aij = take(d.N * 2 * S);
-    L.vpre0 = tape ? take(E * 3 * d.VIN0) : -1;
-    L.x0 = take(E * d.K0);
-    for (int k = 1; k < 4; ++k) L.x[k] = (tape || k == 1) ? take(E * KX) : L.x[1];
+    L.wij = ar.take((int64_t)2 * S * S);
+    L.wr0 = ar.take((int64_t)S * d.K0);
+    L.aij = ar.take(d.N * 2 * S);
+    L.vpre0 = tape ? ar.take(E * 3 * d.VIN0) : -1;
+    L.x0 = ar.take(E * d.K0);
+    for (int k = 1; k < 4; ++k) L.x[k] = (tape || k == 1) ? ar.take(E * KX) : L.x[1];
     L.x[0] = -1;
     L.vst[0] = -1;
-    for (int k = 1; k < 4; ++k) L.vst[k] = (tape || k == 1) ? take(E * 3 * V) : L.vst[1];
-    for (int k = 0; k < 4; ++k) L.vh[k] = (tape || k == 0) ? take(E * 3 * (k ? H : d.H0)) : L.vh[0];
-    for (int k = 0; k < 4; ++k) L.spre[k] = (tape || k == 0) ? take(E * S) : L.spre[0];
-    for (int k = 0; k < 4; ++k) L.gate[k] = (tape || k == 0) ? take(E * V) : L.gate[0];
-    L.g = take(E * S);                       // silu(S_pre): input of the gate GEMM (recomputed in the backward)
-    L.att = take(E);
-    L.total = o;
+    for (int k = 1; k < 4; ++k) L.vst[k] = (tape || k == 1) ? ar.take(E * 3 * V) : L.vst[1];
+    for (int k = 0; k < 4; ++k) L.vh[k] = (tape || k == 0) ? ar.take(E * 3 * (k ? H : d.H0)) : L.vh[0];
+    for (int k = 0; k < 4; ++k) L.spre[k] = (tape || k == 0) ? ar.take(E * S) : L.spre[0];
+    for (int k = 0; k < 4; ++k) L.gate[k] = (tape || k == 0) ? ar.take(E * V) : L.gate[0];
+    L.g = ar.take(E * S);                       // silu(S_pre): input of the gate GEMM (recomputed in the backward)
+    L.att = ar.take(E);
+    L.total = ar.o;
     return L;
 }
 // the final message state: X[3]'s scalar columns are not it (msg3 adds a residual) -- it lives in `sfin`, after the layout above
@@ -72,35 +73,30 @@ inline void weight_sizes(const Dims& d, int64_t* n) {
 }
 inline int64_t weight_total(const Dims& d) { int64_t n[NW], t = 0; weight_sizes(d, n); for (int i = 0; i < NW; ++i) t += n[i]; return t; }
 
-constexpr int WG_SLICES = 16;            // split-K slices of the grouped weight-gradient GEMM (fixed: the reduction order never changes)
 struct BwdLayout {
     int64_t one, ds, dv, dg, dx, dspre[4], gk[4], dgate[4], dup[4], dvh[4], du[4], dlog, dvrow, dvcol, rscs, part, total;
 };
 inline BwdLayout bwd_layout(const Dims& d) {
     BwdLayout L;
-    int64_t o = 0;
-    auto take = [&](int64_t n) { const int64_t r = o; o += a4(n); return r; };
+    Arena ar;
     const int64_t E = d.E;
-    L.one = take(1);                         // 1.0f: the B operand of the bias gradients (stride 0)
-    L.ds = take(E * S);
-    L.dv = take(E * 3 * V);
-    L.dg = take(E * S);
-    L.dx = take(E * (KX > d.K0 ? KX : d.K0));
+    L.one = ar.take(1);                         // 1.0f: the B operand of the bias gradients (stride 0)
+    L.ds = ar.take(E * S);
+    L.dv = ar.take(E * 3 * V);
+    L.dg = ar.take(E * S);
+    L.dx = ar.take(E * (KX > d.K0 ? KX : d.K0));
     for (int k = 0; k < 4; ++k) {
-        L.dspre[k] = take(E * S); L.gk[k] = take(E * S); L.dgate[k] = take(E * V); L.dup[k] = take(E * 3 * V);
-        L.dvh[k] = take(E * 3 * (k ? H : d.H0)); L.du[k] = take(E * 3 * SV);
+        L.dspre[k] = ar.take(E * S); L.gk[k] = ar.take(E * S); L.dgate[k] = ar.take(E * V); L.dup[k] = ar.take(E * 3 * V);
+        L.dvh[k] = ar.take(E * 3 * (k ? H : d.H0)); L.du[k] = ar.take(E * 3 * SV);
     }
-    L.dlog = take(E);
-    L.dvrow = take(E * 3 * V);
-    L.dvcol = take(E * 3 * V);
-    L.rscs = take(d.N * 2 * S);
-    L.part = take((int64_t)WG_SLICES * weight_total(d));
-    L.total = o;
+    L.dlog = ar.take(E);
+    L.dvrow = ar.take(E * 3 * V);
+    L.dvcol = ar.take(E * 3 * V);
+    L.rscs = ar.take(d.N * 2 * S);
+    L.part = ar.take((int64_t)WG_SLICES * weight_total(d));
+    L.total = ar.o;
     return L;
 }
-
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + expf(-x)); }
-__device__ __forceinline__ float sigm_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- pack: WIJ [2S][S] = [W_i ; W_j] (rows: output channel of the node half), WR0 [S][K0] = W_s0 columns [e | |vh| | q] ----------------------
 __global__ void k_mp_pack(const float* __restrict__ ws0, float* __restrict__ wij, float* __restrict__ wr0, Dims d) {
@@ -176,7 +172,7 @@ __global__ void k_mp_act(int k, Dims d, float* __restrict__ spre, const float* _
     float v = spre[i];
     if (!k) v = v + aij[row[e] * 2 * S + c] + aij[col[e] * 2 * S + S + c] + b0[c];
     spre[i] = v;
-    const float a = silu_f(v);
+    const float a = act_f(ACT_SILU, v);
     g[i] = a;
     s_out[e * ld_out + c] = (k ? s_in[e * ld_in + c] : 0.f) + a;
 }
@@ -290,9 +286,8 @@ __global__ void k_mp_act_bwd(Dims d, const float* __restrict__ spre, const float
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d.E * S) return;
     const float x = spre[i];
-    const float sg = 1.f / (1.f + expf(-x));
-    g[i] = silu_f(x);
-    dspre[i] = (ds[i] + dgin[i]) * (sg * (1.f + x * (1.f - sg)));
+    g[i] = act_f(ACT_SILU, x);
+    dspre[i] = (ds[i] + dgin[i]) * act_df(ACT_SILU, x);
 }
 
 // ---- backward: norms, frame scalars and down projections of GCP k (one wave per edge, 4 per workgroup) -------------------------------------
@@ -395,101 +390,6 @@ __global__ void k_mp_node_sum(Dims d, const int32_t* __restrict__ rowptr, const 
     }
 }
 
-// ---- grouped split-K GEMM for every weight gradient of the layer: C_g = A_g . B_g into part[z] + off_g (row stride ldc_g) ----------------------
-// One workgroup per (64 x 64 tile of some group, K slice z); slice z of every group covers the same fraction of that group's K, the slices are
-// added in slice order by gops::k_reduce_slices (deterministic).  The tile body is gops::k_gemm's.
-constexpr int MAXG = 36;
-struct WgDesc {
-    const float* A; const float* B;
-    int64_t sam, sak, sbk, sbn, K, off;
-    int M, N, ldc, tile0;
-};
-struct WgTable {
-    WgDesc g[MAXG];
-    int n, tiles;
-    int64_t total;
-};
-
-__global__ __launch_bounds__(256) void k_mp_wgrad(WgTable T, float* __restrict__ part) {
-    using namespace gops;
-    __shared__ float As[2][GK][GM + 1];
-    __shared__ float Bs[2][GK][GN + 1];
-    int gi = 0;
-    while (gi + 1 < T.n && T.g[gi + 1].tile0 <= (int)blockIdx.x) ++gi;
-    const WgDesc& D = T.g[gi];
-    const int t = blockIdx.x - D.tile0, tn_count = (D.N + GN - 1) / GN;
-    const int64_t M = D.M, K = D.K;
-    const int N = D.N;
-    const float* A = D.A;
-    const float* B = D.B;
-    const int64_t sam = D.sam, sak = D.sak, sbk = D.sbk, sbn = D.sbn;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int64_t m0 = (int64_t)(t / tn_count) * GM;
-    const int n0 = (t % tn_count) * GN;
-    const int64_t kslice = ((K + WG_SLICES - 1) / WG_SLICES + GK - 1) / GK * GK;
-    const int64_t k_begin = (int64_t)blockIdx.z * kslice, k_end = k_begin + kslice < K ? k_begin + kslice : K;
-    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int am[4], ak[4], bn[4], bk[4];
-    const float* pa[4];
-    const float* pb[4];
-    bool va[4], vb[4];
-    const bool a_kfast = sak == 1, b_nfast = sbn == 1;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = tid + 256 * i;
-        am[i] = a_kfast ? idx / GK : idx % GM; ak[i] = a_kfast ? idx % GK : idx / GM;
-        bn[i] = b_nfast ? idx % GN : idx / GK; bk[i] = b_nfast ? idx / GN : idx % GK;
-        va[i] = m0 + am[i] < M; vb[i] = n0 + bn[i] < N;
-        pa[i] = A + (va[i] ? (m0 + am[i]) * sam : 0) + (k_begin + ak[i]) * sak;
-        pb[i] = B + (k_begin + bk[i]) * sbk + (vb[i] ? (int64_t)(n0 + bn[i]) * sbn : 0);
-    }
-    const int64_t da = GK * sak, db_ = GK * sbk;
-    float ra[4], rb[4];
-    auto fetch = [&](int64_t k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            ra[i] = (va[i] && k0 + ak[i] < k_end) ? *pa[i] : 0.f;
-            rb[i] = (vb[i] && k0 + bk[i] < k_end) ? *pb[i] : 0.f;
-            pa[i] += da; pb[i] += db_;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { As[buf][ak[i]][am[i]] = ra[i]; Bs[buf][bk[i]][bn[i]] = rb[i]; }
-    };
-    if (k_begin < k_end) fetch(k_begin);
-    else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { ra[i] = 0.f; rb[i] = 0.f; }
-    }
-    stash(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t k0 = k_begin; k0 < k_end; k0 += GK) {
-        const bool more = k0 + GK < k_end;
-        if (more) fetch(k0 + GK);
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2) {
-            const float a = As[buf][kk + (lane >> 5)][wm * 32 + (lane & 31)];
-            const float b = Bs[buf][kk + (lane >> 5)][wn * 32 + (lane & 31)];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
-        if (more) stash(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-    float* Cz = part + (int64_t)blockIdx.z * T.total + D.off;
-    const int colx = n0 + wn * 32 + (lane & 31);
-    if (colx < N) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int64_t rw = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (rw < M) Cz[rw * D.ldc + colx] = acc[r];
-        }
-    }
-}
-
 }  // namespace gmp
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -504,14 +404,6 @@ static inline bool gmp_weights_ok(const float* const* w) {
         if (!w[i]) return false;
     return true;
 }
-// y[M, Nn] = A . B (+ bias) on gops::k_gemm, one K slice
-static inline void gmp_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, float* Cm, const float* bias, int64_t M,
-                            int Nn, int64_t K, hipStream_t st) {
-    const int64_t kslice = (K + gops::GK - 1) / gops::GK * gops::GK;
-    const dim3 grid((unsigned)((M + gops::GM - 1) / gops::GM), (unsigned)((Nn + gops::GN - 1) / gops::GN), 1);
-    hipLaunchKernelGGL(gops::k_gemm, grid, dim3(256), 0, st, A, sam, sak, B, sbk, sbn, Cm, bias, M, Nn, K, kslice);
-}
-
 extern "C" {
 
 int64_t gcdm_mp_workspace_bytes(int32_t which, int64_t N, int64_t E, int32_t SE, int32_t VE) {
@@ -538,7 +430,7 @@ int gcdm_mp_fwd(const float* h, const float* vnode, const float* e, const float*
     float* vfin = ws + fwd_vfin(d, L);
     const int64_t npack = (int64_t)2 * S * S + (int64_t)S * d.K0;
     hipLaunchKernelGGL(k_mp_pack, dim3(gops_blocks(npack)), dim3(256), 0, st, W[2], ws + L.wij, ws + L.wr0, d);
-    gmp_gemm(h, S, 1, ws + L.wij, 1, S, ws + L.aij, nullptr, N, 2 * S, S, st);                  // [A_i | A_j] = h [W_i ; W_j]^T
+    gemm(h, S, 1, ws + L.wij, 1, S, ws + L.aij, nullptr, N, 2 * S, S, st);                  // [A_i | A_j] = h [W_i ; W_j]^T
     const unsigned eb = (unsigned)((E + 3) / 4);
     for (int k = 0; k < 4; ++k) {
         const float* const* Wk = W + 7 * k;
@@ -549,12 +441,12 @@ int gcdm_mp_fwd(const float* h, const float* vnode, const float* e, const float*
         float* gate = ws + L.gate[k];
         hipLaunchKernelGGL(k_mp_down, dim3(eb), dim3(256), 0, st, k, d, vnode, xi, e, row, col, frames, edge_mask, vin, Wk[0], Wk[1],
                            (k == 0 && tape) ? ws + L.vpre0 : nullptr, ws + L.vh[k], X);
-        if (k == 0) gmp_gemm(X, d.K0, 1, ws + L.wr0, 1, d.K0, spre, nullptr, E, S, d.K0, st);
-        else gmp_gemm(X, KX, 1, Wk[2], 1, KX, spre, Wk[3], E, S, KX, st);
+        if (k == 0) gemm(X, d.K0, 1, ws + L.wr0, 1, d.K0, spre, nullptr, E, S, d.K0, st);
+        else gemm(X, KX, 1, Wk[2], 1, KX, spre, Wk[3], E, S, KX, st);
         float* s_out = k < 3 ? ws + L.x[k + 1] : sfin;
         hipLaunchKernelGGL(k_mp_act, dim3(gops_blocks(E * S)), dim3(256), 0, st, k, d, spre, ws + L.aij, W[3], row, col, ws + L.g, X, (int)KX, s_out,
                            k < 3 ? (int)KX : (int)S);
-        gmp_gemm(ws + L.g, S, 1, Wk[5], 1, S, gate, Wk[6], E, V, S, st);
+        gemm(ws + L.g, S, 1, Wk[5], 1, S, gate, Wk[6], E, V, S, st);
         hipLaunchKernelGGL(k_mp_vout, dim3(gops_blocks(E * V)), dim3(256), 0, st, k, d, ws + L.vh[k], Wk[4], gate, vin, vout);
     }
     hipLaunchKernelGGL(k_mp_att, dim3(eb), dim3(256), 0, st, d, sfin, W[28], W[29], ws + L.att);
@@ -583,60 +475,50 @@ int gcdm_mp_bwd(const float* dagg, const float* h, const int64_t* row, const int
                        ws + L.one);
     for (int k = 3; k >= 0; --k) {
         const float* const* Wk = W + 7 * k;
-        const int ldx = k ? KX : d.K0;
         hipLaunchKernelGGL(k_mp_vout_bwd, dim3(gops_blocks(E * V)), dim3(256), 0, st, k, d, t + F.vh[k], Wk[4], t + F.gate[k], ws + L.dv, ws + L.dup[k],
                            ws + L.dgate[k]);
-        gmp_gemm(ws + L.dgate[k], V, 1, Wk[5], S, 1, ws + L.dg, nullptr, E, S, V, st);                 // d gate_in = d gate . W_g
+        gemm(ws + L.dgate[k], V, 1, Wk[5], S, 1, ws + L.dg, nullptr, E, S, V, st);                 // d gate_in = d gate . W_g
         hipLaunchKernelGGL(k_mp_act_bwd, dim3(gops_blocks(E * S)), dim3(256), 0, st, d, t + F.spre[k], ws + L.ds, ws + L.dg, ws + L.dspre[k], ws + L.gk[k]);
-        if (k) gmp_gemm(ws + L.dspre[k], S, 1, Wk[2], KX, 1, ws + L.dx, nullptr, E, KX, S, st);          // dX = dS_pre . W_s
-        else gmp_gemm(ws + L.dspre[0], S, 1, t + F.wr0, d.K0, 1, ws + L.dx, nullptr, E, d.K0, S, st);
-        (void)ldx;
+        if (k) gemm(ws + L.dspre[k], S, 1, Wk[2], KX, 1, ws + L.dx, nullptr, E, KX, S, st);          // dX = dS_pre . W_s
+        else gemm(ws + L.dspre[0], S, 1, t + F.wr0, d.K0, 1, ws + L.dx, nullptr, E, d.K0, S, st);
         hipLaunchKernelGGL(k_mp_down_bwd, dim3(eb), dim3(256), 0, st, k, d, ws + L.dx, ws + L.dup[k], t + F.vh[k], Wk[4], Wk[0], Wk[1], frames, edge_mask,
                            ws + L.dvh[k], ws + L.du[k], ws + L.ds, ws + L.dv, de, dxi, ws + L.dvrow, ws + L.dvcol);
     }
     hipLaunchKernelGGL(k_mp_node_sum, dim3(gops_blocks(N * (S + 3 * V))), dim3(256), 0, st, d, rowptr, colptr, colperm, ws + L.dspre[0], ws + L.dvrow,
                        ws + L.dvcol, ws + L.rscs, dvnode);
-    gmp_gemm(ws + L.rscs, 2 * S, 1, t + F.wij, S, 1, dh, nullptr, N, S, 2 * S, st);                    // dh = [RS | CS] . [W_i ; W_j]
+    gemm(ws + L.rscs, 2 * S, 1, t + F.wij, S, 1, dh, nullptr, N, S, 2 * S, st);                    // dh = [RS | CS] . [W_i ; W_j]
 
     // every weight gradient of the layer: one grouped split-K launch, one fixed-order slice reduction
     int64_t sz[NW], off[NW];
     weight_sizes(d, sz);
-    off[0] = 0;
-    for (int i = 1; i < NW; ++i) off[i] = off[i - 1] + sz[i - 1];
     WgTable T;
-    T.n = 0; T.tiles = 0; T.total = weight_total(d);
-    auto add = [&](const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, int M, int Nn, int64_t K, int64_t o, int ldc) {
-        WgDesc& g = T.g[T.n++];
-        g.A = A; g.B = B; g.sam = sam; g.sak = sak; g.sbk = sbk; g.sbn = sbn; g.K = K; g.off = o; g.M = M; g.N = Nn; g.ldc = ldc; g.tile0 = T.tiles;
-        T.tiles += ((M + gops::GM - 1) / gops::GM) * ((Nn + gops::GN - 1) / gops::GN);
-    };
+    T.total = wgrad_offsets(sz, NW, off);
     const float* one = ws + L.one;
     for (int k = 0; k < 4; ++k) {
         const int hk = k ? H : d.H0, vin = k ? V : d.VIN0;
         const float* vpre = k ? t + F.vst[k] : t + F.vpre0;
         const float* dsp = ws + L.dspre[k];
         const int64_t ow = off[7 * k + 2];
-        add(ws + L.dvh[k], 1, hk, vpre, vin, 1, hk, vin, 3 * E, off[7 * k + 0], vin);                     // dW_down = sum_(e,x) dvh^T v_pre
-        add(ws + L.du[k], 1, SV, vpre, vin, 1, SV, vin, 3 * E, off[7 * k + 1], vin);                       // dW_down_frames
+        T.add(ws + L.dvh[k], 1, hk, vpre, vin, 1, hk, vin, 3 * E, off[7 * k + 0], vin);                     // dW_down = sum_(e,x) dvh^T v_pre
+        T.add(ws + L.du[k], 1, SV, vpre, vin, 1, SV, vin, 3 * E, off[7 * k + 1], vin);                       // dW_down_frames
         if (k) {
-            add(dsp, 1, S, t + F.x[k], KX, 1, S, KX, E, ow, KX);                                           // dW_s = dS_pre^T X
+            T.add(dsp, 1, S, t + F.x[k], KX, 1, S, KX, E, ow, KX);                                           // dW_s = dS_pre^T X
         } else {
             const float* rscs = ws + L.rscs;
             const float* x0 = t + F.x0;
-            add(rscs, 1, 2 * S, h, S, 1, S, S, N, ow, d.KIN0);                                              // W_i: (row sums)^T h
-            add(dsp, 1, S, x0, d.K0, 1, S, SE, E, ow + S, d.KIN0);                                         // W_e
-            add(rscs + S, 1, 2 * S, h, S, 1, S, S, N, ow + S + SE, d.KIN0);                                 // W_j: (column sums)^T h
-            add(dsp, 1, S, x0 + SE, d.K0, 1, S, d.H0 + 3 * SV, E, ow + 2 * S + SE, d.KIN0);               // [|vh| | q] columns
+            T.add(rscs, 1, 2 * S, h, S, 1, S, S, N, ow, d.KIN0);                                              // W_i: (row sums)^T h
+            T.add(dsp, 1, S, x0, d.K0, 1, S, SE, E, ow + S, d.KIN0);                                         // W_e
+            T.add(rscs + S, 1, 2 * S, h, S, 1, S, S, N, ow + S + SE, d.KIN0);                                 // W_j: (column sums)^T h
+            T.add(dsp, 1, S, x0 + SE, d.K0, 1, S, d.H0 + 3 * SV, E, ow + 2 * S + SE, d.KIN0);               // [|vh| | q] columns
         }
-        add(dsp, 1, S, one, 0, 0, S, 1, E, off[7 * k + 3], 1);                                             // b_s
-        add(ws + L.dup[k], 1, V, t + F.vh[k], hk, 1, V, hk, 3 * E, off[7 * k + 4], hk);                    // dW_up = sum dup^T vh
-        add(ws + L.dgate[k], 1, V, ws + L.gk[k], S, 1, V, S, E, off[7 * k + 5], S);                        // dW_gate = dgate^T silu(S_pre)
-        add(ws + L.dgate[k], 1, V, one, 0, 0, V, 1, E, off[7 * k + 6], 1);                                // b_gate
+        T.add(dsp, 1, S, one, 0, 0, S, 1, E, off[7 * k + 3], 1);                                             // b_s
+        T.add(ws + L.dup[k], 1, V, t + F.vh[k], hk, 1, V, hk, 3 * E, off[7 * k + 4], hk);                    // dW_up = sum dup^T vh
+        T.add(ws + L.dgate[k], 1, V, ws + L.gk[k], S, 1, V, S, E, off[7 * k + 5], S);                        // dW_gate = dgate^T silu(S_pre)
+        T.add(ws + L.dgate[k], 1, V, one, 0, 0, V, 1, E, off[7 * k + 6], 1);                                // b_gate
     }
-    add(ws + L.dlog, 0, 1, t + fwd_sfin(F), S, 1, 1, S, E, off[28], S);                                     // attention weight
-    add(ws + L.dlog, 0, 1, one, 0, 0, 1, 1, E, off[29], 1);                                                 // attention bias
-    hipLaunchKernelGGL(k_mp_wgrad, dim3((unsigned)T.tiles, 1, WG_SLICES), dim3(256), 0, st, T, ws + L.part);
-    hipLaunchKernelGGL(gops::k_reduce_slices, dim3(gops_blocks(T.total)), dim3(256), 0, st, ws + L.part, dweights, T.total, (int)WG_SLICES);
+    T.add(ws + L.dlog, 0, 1, t + fwd_sfin(F), S, 1, 1, S, E, off[28], S);                                     // attention weight
+    T.add(ws + L.dlog, 0, 1, one, 0, 0, 1, 1, E, off[29], 1);                                                 // attention bias
+    wgrad_launch(T, ws + L.part, dweights, st);
     return GOPS_LAUNCH_OK();
 }
 

@@ -16,7 +16,7 @@ for line in log.splitlines():
         cur = m.group(1)
         rows[cur] = {}
         continue
-    m = re.search(r"remark:\s+([\w][\w \[\]/]*?): (\S+)", line)
+    m = re.search(r"remark:\s+(?:\S+:\d+:\d+:\s+)?([\w][\w \[\]/]*?): (\S+)", line)      # with or without the source location
     if m and cur:
         rows[cur][m.group(1)] = m.group(2)
 for k, v in rows.items():
