@@ -38,7 +38,8 @@
  *   p -= lr / (1 - beta1^step) * m / (sqrt(vmax or v) / sqrt(1 - beta2^step) + eps)
  * and then, when ema = 1 and the k-th completed step has k >= ema_start and k % ema_every == 0, for every tensor (with a gradient or not):
  *   ema -= (1 - ema_decay) (ema - p).
- * With clip = 1 the step pushes min(norm, max_norm) onto the queue.
+ * With clip = 1 the step pushes min(norm, max_norm) onto the queue.  With clip = 1 the caller seeds at least one queue value (qcount >= 1):
+ * the mean and the deviation divide by qcount, and the result with an empty queue is unspecified.
  *
  * gcdm_optim_ema_swap: mode 0 swaps p and ema, 1 copies p into ema, 2 copies ema into p (every tensor of the table). */
 #ifndef GCDM_OPTIM_H

@@ -1,6 +1,7 @@
 """fp64 restatement of the reference's update after backward() -- what optim.TrainingUpdate computes -- with a running bound on the error of
 an fp32 evaluation of the same step (tests/test_optim_cpu.py checks the restatement against torch.optim.AdamW and clip_grad_norm_ in fp64;
-tests/test_optim_gpu.py checks the HIP update against it).
+tests/test_optim_gpu.py and tests/test_optim_cabi_gpu.py check the HIP update against it), and Emu32, the same step in numpy float32 on
+the buffers of include/gcdm_optim.h, which the CPU tests hold to the bars the device is held to.
 
 The reference (qm9_mol_gen_ddpm.py configure_gradient_clipping, models/__init__.py Queue, utils/__init__.py EMA):
     max_norm = 1.5 * mean(Q) + 2 * std(Q)   (numpy, population std; Q seeded with 3000, the last `queue_len` values, newest first)
@@ -65,6 +66,7 @@ class RefUpdate:
         self.queue.add(3000.0)
         self.err_p, self.err_m, self.err_v, self.err_vmax, self.err_ema = z(), z(), z(), z(), z()
         self.norms, self.coefs, self.max_norms = [], [], []
+        self.norms64 = []          # the norm before its rounding to fp32: what the 41u bound of the docstring is relative to
 
     def step(self, grads: List[Optional[torch.Tensor]]) -> bool:
         gs = [None if g is None else g.detach().double() for g in grads]
@@ -82,6 +84,7 @@ class RefUpdate:
             self.queue.add(min(norm32, max_norm))
             self.max_norms.append(float(max_norm))
         self.norms.append(norm32)
+        self.norms64.append(norm)
         self.coefs.append(coef)
         ema_now = False
         self.gstep += 1
@@ -125,3 +128,127 @@ class RefUpdate:
         self.err_p[t] = (self.err_p[t] + 3 * U * self.p[t].abs()
                          + ss * (self.err_m[t] / den + self.m[t].abs() / den * rel_den + 3 * U * self.m[t].abs() / den))
         self.p[t] = self.p[t] - upd
+
+
+class Emu32:
+    """One step of include/gcdm_optim.h restated operation by operation in numpy float32, on the header's own buffers: parameters as a list of
+    fp32 arrays, the state as four quarters of `total` floats with tensor t at offsets[t], the chunk table, the ring with qhead / qcount and
+    the scalars of the 64-byte block.  The norm is an fp32 sum per chunk, then an fp64 sum of the partials.  tests/test_optim_cpu.py holds it
+    to the bars the GPU tests use (a correct fp32 evaluation must pass them) and, with `mutant` set to one of MUTANTS, shows that the same
+    checks reject that wrong evaluation.  It assumes 16-byte aligned pointers where a mutant depends on the float4 body (a, j)."""
+
+    MUTANTS = {"a": "the tail of the update starts at 0 after the float4 body", "b": "EMA only for tensors with a gradient",
+               "c": "steps[t] advances without a gradient", "d": "ema_now tested on gstep before the increment",
+               "e": "bias correction from the global step count", "f": "vmax stored with amsgrad = 0", "g": "swap mode 2 also writes ema",
+               "h": "the queue push stores max_norm", "i": "the ema pointer omits the tensor's offset",
+               "j": "the scalar tail of the norm starts at 0 after the vector body"}
+
+    def __init__(self, params, offsets, total, chunks, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=True, clip=True,
+                 queue_len=50, ema=True, ema_decay=0.9, ema_every=1, ema_start=0, mutant=None):
+        assert mutant is None or mutant in self.MUTANTS
+        self.p = [np.array(q, dtype=np.float32).reshape(-1).copy() for q in params]
+        self.numel = [q.size for q in self.p]
+        self.offsets, self.total, self.chunks = list(offsets), int(total), [tuple(int(x) for x in c) for c in chunks]
+        self.state = np.zeros((4, self.total), dtype=np.float32)
+        self.lr, (self.b1, self.b2), self.eps, self.wd = lr, betas, eps, weight_decay
+        self.amsgrad, self.clip, self.queue_len = bool(amsgrad), bool(clip), int(queue_len)
+        self.ema_on, self.ema_decay, self.ema_every, self.ema_start = bool(ema), ema_decay, int(ema_every), int(ema_start)
+        self.mutant = mutant
+        T = len(self.p)
+        self.steps = np.zeros(T, dtype=np.int64)
+        self.tscal = np.full((T, 2), np.nan)
+        self.ring = np.zeros(self.queue_len)
+        self.norm, self.max_norm, self.coef = 0.0, 0.0, np.float32(0)
+        self.flags = self.qhead = self.qcount = self.gstep = self.skipped = self.ema_applied = 0
+
+    def view(self, k, t):
+        return self.state[k, self.offsets[t]: self.offsets[t] + self.numel[t]]
+
+    def step(self, grads):
+        f32 = np.float32
+        gs = [None if g is None else np.asarray(g, dtype=f32).reshape(-1) for g in grads]
+        sq = 0.0
+        with np.errstate(all="ignore"):
+            for t, s, n in self.chunks:
+                if gs[t] is None:
+                    continue
+                x = gs[t][s:s + n]
+                part = np.sum(x * x, dtype=f32)
+                if self.mutant == "j" and n % 4:
+                    part = f32(part + np.sum(x[: n // 4 * 4] * x[: n // 4 * 4], dtype=f32))
+                sq += float(part)
+            norm = f32(math.sqrt(sq)) if sq == sq and sq >= 0 else f32(np.nan)
+        self.norm = float(norm)
+        self.skipped, self.ema_applied = int(not np.isfinite(norm)), 0
+        if self.skipped:
+            self.flags |= 1
+            return False
+        coef = f32(1)
+        if self.clip:
+            n = self.qcount
+            mean = 0.0
+            for i in range(n):
+                mean += self.ring[i]
+            mean /= n
+            var = 0.0
+            for i in range(n):
+                var += (self.ring[i] - mean) ** 2
+            self.max_norm = 1.5 * mean + 2.0 * math.sqrt(var / n)
+            inv = f32(1) / (norm + f32(1e-6))
+            coef = min(f32(1), inv * f32(self.max_norm))
+            self.ring[self.qhead] = self.max_norm if self.mutant == "h" else min(float(norm), self.max_norm)
+            self.qhead = (self.qhead + 1) % self.queue_len
+            self.qcount = min(self.qcount + 1, self.queue_len)
+        self.coef = coef
+        k_ema = self.gstep if self.mutant == "d" else self.gstep + 1
+        self.gstep += 1
+        self.ema_applied = int(self.ema_on and k_ema >= self.ema_start and k_ema % self.ema_every == 0)
+        for t, g in enumerate(gs):
+            if g is None and self.mutant != "c":
+                continue
+            self.steps[t] += 1
+            k = self.gstep if self.mutant == "e" else int(self.steps[t])
+            self.tscal[t] = (self.lr / (1.0 - self.b1 ** k), math.sqrt(1.0 - self.b2 ** k))
+        hyp = dict(coef=coef, decay_mul=f32(1.0 - self.lr * self.wd), omb1=f32(1.0 - self.b1), b2=f32(self.b2), omb2=f32(1.0 - self.b2),
+                   eps=f32(self.eps), ema_w=f32(1.0 - self.ema_decay))
+        for t, s, n in self.chunks:
+            has_grad = gs[t] is not None
+            if not has_grad and not self.ema_applied:
+                continue
+            self._chunk(t, s, n, gs[t], hyp)
+            if self.mutant == "a" and n % 4 and n >= 4:
+                self._chunk(t, s, n // 4 * 4, gs[t], hyp)
+        return True
+
+    def _chunk(self, t, s, n, g, h):
+        f32 = np.float32
+        o = self.offsets[t] + s
+        p = self.p[t][s:s + n]
+        m, v, vm = (self.state[k, o:o + n] for k in range(3))
+        e = self.state[3, s:s + n] if self.mutant == "i" else self.state[3, o:o + n]
+        has_grad = g is not None
+        if has_grad:
+            ss, sbc2 = f32(self.tscal[t, 0]), f32(self.tscal[t, 1])
+            gg = g[s:s + n] * h["coef"]
+            p[:] = p * h["decay_mul"]
+            m[:] = m + h["omb1"] * (gg - m)
+            v[:] = v * h["b2"] + gg * gg * h["omb2"]
+            if self.amsgrad:
+                vm[:] = np.maximum(vm, v)
+                den = np.sqrt(vm) / sbc2 + h["eps"]
+            else:
+                den = np.sqrt(v) / sbc2 + h["eps"]
+                if self.mutant == "f":
+                    vm[:] = 0
+            p[:] = p + (-ss) * (m / den)
+        if self.ema_applied and (has_grad or self.mutant != "b"):
+            e[:] = e - (e - p) * h["ema_w"]
+
+    def swap(self, mode):
+        """gcdm_optim_ema_swap: 0 swaps p and ema, 1 copies p into ema, 2 copies ema into p."""
+        for t in range(len(self.p)):
+            x, y = self.p[t].copy(), self.view(3, t).copy()
+            if mode != 1:
+                self.p[t][:] = y
+            if mode != 2 or self.mutant == "g":
+                self.view(3, t)[:] = x

@@ -14,6 +14,7 @@ import subprocess
 import pytest
 import torch
 
+import optim_cases as K
 import optim_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,6 +220,103 @@ def test_fp64_oracle_matches_torch_adamw_clip_and_ema_over_60_steps():
         assert int(st["step"]) == 60
         for mine, theirs in ((ref.m[t], st["exp_avg"]), (ref.v[t], st["exp_avg_sq"]), (ref.vmax[t], st["max_exp_avg_sq"])):
             assert (mine - theirs).abs().max().item() <= 1e-6 * theirs.abs().max().item(), t
+
+
+@pytest.mark.parametrize("every,start", [(1, 0), (3, 0), (2, 5), (4, 4)])
+def test_fp64_oracle_matches_torch_with_an_ema_schedule_and_intermittent_gradients(every, start):
+    """torch.optim.AdamW keeps a step count per parameter and passes over a parameter whose grad is None, as the oracle does; the EMA is
+    applied in the torch loop on the k-th step only when k >= ema_start and k % ema_every == 0."""
+    shapes = [(7, 5), (3,), (1,), (4, 4, 2)]
+    have = lambda t, k: {0: True, 1: k in (1, 2, 4, 6, 11), 2: False, 3: k == 5}[t]          # noqa: E731
+    g0 = torch.Generator().manual_seed(5)
+    init = [torch.randn(s, generator=g0, dtype=torch.float64) for s in shapes]
+    kw = dict(lr=1e-2, weight_decay=1e-2, ema_decay=0.9)
+    ref = optim_ref.RefUpdate(init, ema_every=every, ema_start=start, **kw)
+    params = [torch.nn.Parameter(p.clone()) for p in init]
+    opt = torch.optim.AdamW(params, lr=1e-2, weight_decay=1e-2, amsgrad=True, foreach=False)
+    ema = [p.detach().clone() + 0.5 for p in params]
+    ref.ema = [e.clone() for e in ema]
+    queue = optim_ref.Queue()
+    queue.add(3000)
+    applied = []
+    for k in range(1, 13):
+        grads = [torch.randn(s, generator=g0, dtype=torch.float64) * (40.0 if k == 9 else 1.0) if have(t, k) else None for t, s in enumerate(shapes)]
+        for p, g in zip(params, grads):
+            p.grad = None if g is None else g.clone()
+        max_norm = 1.5 * queue.mean() + 2 * queue.std()
+        norm = float(torch.nn.utils.clip_grad_norm_([p for p in params if p.grad is not None], max_norm))
+        queue.add(float(max_norm) if norm > max_norm else norm)
+        opt.step()
+        if k >= start and k % every == 0:
+            applied.append(k)
+            for e, p in zip(ema, params):
+                e.sub_((e - p.detach()).mul_(1.0 - 0.9))
+        assert ref.step(grads)
+    assert applied == [k for k in range(1, 13) if k >= start and k % every == 0] and 0 < len(applied)
+    assert ref.gstep == 12 and ref.steps == [12, 5, 0, 1]
+    assert ref.queue.items == pytest.approx(queue.items, rel=1e-6)
+    for t, p in enumerate(params):
+        scale = max(1.0, float(p.detach().abs().max()))
+        assert (ref.p[t] - p.detach()).abs().max().item() <= 1e-6 * scale, t
+        assert (ref.ema[t] - ema[t]).abs().max().item() <= 1e-6 * scale, t
+        if ref.steps[t] == 0:
+            assert torch.equal(ref.p[t], init[t]) and p not in opt.state
+            continue
+        st = opt.state[p]
+        assert int(st["step"]) == ref.steps[t]
+        for mine, theirs in ((ref.m[t], st["exp_avg"]), (ref.v[t], st["exp_avg_sq"]), (ref.vmax[t], st["max_exp_avg_sq"])):
+            assert (mine - theirs).abs().max().item() <= 1e-6 * theirs.abs().max().item(), t
+
+
+# ---- the fp32 restatement (optim_ref.Emu32) through the cases of the GPU file (tests/optim_cases.py) ----------------------------------------------
+def test_the_tables_hold_the_shapes_the_cases_rely_on():
+    """Chunking B has short chunks, chunks whose float4 count is no multiple of 256, several chunks in one small tensor and a shuffled table;
+    the 300-tensor table has more than 256 tensors and chunks; no chunk exceeds the 16384 values the norm's error bound assumes."""
+    b = K.chunks_b(K.NUMELS)
+    K.check_chunks(K.NUMELS, b)
+    assert {4, 8, 260, 1028, 16384} <= {n for _, _, n in b} and [t for t, _, _ in b] != sorted(t for t, _, _ in b)
+    assert sum(1 for t, _, _ in b if K.NUMELS[t] == 64) >= 3 and any(n % 4 for _, _, n in b)
+    many = K.many_tensors_spec()
+    assert len(many.numels) == 300 and len(many.chunks) > 300 and all(4 <= n <= 8 for n in many.numels)
+    assert max(n for _, _, n in K.chunks_a(K.NUMELS)) == K.CHUNK
+
+
+EMU_CASES = {
+    "layouts": lambda make: K.case_layouts(make, False),
+    "layouts clip": lambda make: K.case_layouts(make, True),
+    "intermittent": K.case_intermittent,
+    "ema 1/0": lambda make: K.case_ema_schedule(make, 1, 0),
+    "ema 3/0": lambda make: K.case_ema_schedule(make, 3, 0),
+    "ema 2/5": lambda make: K.case_ema_schedule(make, 2, 5),
+    "ema 4/4": lambda make: K.case_ema_schedule(make, 4, 4),
+    "ema 3/0 nonfinite": lambda make: K.case_ema_schedule(make, 3, 0, True),
+    "untouched vmax": lambda make: K.case_untouched(make, "vmax"),
+    "untouched ema": lambda make: K.case_untouched(make, "ema"),
+    "swap": K.case_swap,
+    "nonfinite nan": lambda make: K.case_nonfinite(make, "nan_tail"),
+    "nonfinite inf": lambda make: K.case_nonfinite(make, "inf_chunk4"),
+    "300 tensors": K.case_many_tensors,
+}
+EMU_CASES.update({f"queue {k}": (lambda make, k=k: K.case_queue(make, k)) for k in K.QUEUES})
+EMU_CASES.update({f"limit {k}": (lambda make, k=k: K.case_limits(make, k)) for k in K.LIMITS})
+
+
+@pytest.mark.parametrize("case", list(EMU_CASES))
+def test_a_correct_fp32_evaluation_meets_every_bar(case):
+    """Emu32 follows the header's formulas in numpy float32: it must pass every check the device is held to, at the same bars."""
+    EMU_CASES[case](K.EmuRunner)
+
+
+# mutant of Emu32 -> one case whose checks must reject it (the mutants of the library the GPU file is run against: DESIGN.md 3.6)
+MUTANT_CASES = {"a": "layouts", "b": "ema 1/0", "c": "intermittent", "d": "ema 3/0", "e": "intermittent", "f": "untouched vmax", "g": "swap",
+                "h": "queue len3", "i": "ema 2/5", "j": "layouts"}
+
+
+@pytest.mark.parametrize("mutant", sorted(optim_ref.Emu32.MUTANTS))
+def test_the_bars_reject_each_mutant(mutant):
+    assert sorted(MUTANT_CASES) == sorted(optim_ref.Emu32.MUTANTS)
+    with pytest.raises(AssertionError):
+        EMU_CASES[MUTANT_CASES[mutant]](lambda spec: K.EmuRunner(spec, mutant=mutant))
 
 
 def test_module_configure_optimizers_is_the_fused_update_and_needs_the_gpu():
