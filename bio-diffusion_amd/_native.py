@@ -22,7 +22,8 @@ OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(
                os.path.join(_HERE, "csrc", "gcdm_ops.mp_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_train.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.gcp2.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_gcp2_train.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h"),
-               os.path.join(_HERE, "csrc", "gcdm_ops.classifier.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier.h")]
+               os.path.join(_HERE, "csrc", "gcdm_ops.classifier.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.objective.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_objective.h")]
 ABI_VERSION = 2
 
 FLAG_NAN_VEL, FLAG_MEAN_NOT_ZERO, FLAG_COG_DRIFT, FLAG_F16_RANGE = 1, 2, 4, 8
@@ -170,6 +171,18 @@ CLASSIFIER_SIGNATURES = {
 }
 CLASSIFIER_RESTYPES = {"gcdm_classifier_workspace_bytes": C.c_int64, "gcdm_classifier_last_error": C.c_char_p}
 CLASSIFIER_MAX_NODES, CLASSIFIER_MAX_IN_NODE_NF, CLASSIFIER_MAX_HIDDEN_NF = 32, 16, 256      # GCDM_CLASSIFIER_MAX_*
+# the fused diffusion objective: noising, loss terms, backward (include/gcdm_objective.h), exported from the same library
+OBJECTIVE_SIGNATURES = {
+    "gcdm_objective_workspace_bytes": [I64, I64, I32, I32],
+    "gcdm_objective_prepare": [P] * 8 + [I32] + [P] * 12 + [I64, I64, I32, I32, I32, I32, I32, P],
+    "gcdm_objective_terms": [P] * 14 + [I64, I64, I32, I32, I32, I32, P],
+    "gcdm_objective_reduce": [P, P, P, P, P, I64, I32, I32, I32, I32, P],
+    "gcdm_objective_bwd": [P, I64, P, I64, P, I64] + [P] * 8 + [I64, I64, I32, I32, P],
+}
+OBJECTIVE_RESTYPES = {"gcdm_objective_workspace_bytes": C.c_int64}
+OBJECTIVE_MAX_TYPES = 16                                                  # GCDM_OBJECTIVE_MAX_TYPES
+OBJECTIVE_TRAIN_VLB, OBJECTIVE_EVAL, OBJECTIVE_TRAIN_L2 = 0, 1, 2         # GCDM_OBJECTIVE_*
+OBJECTIVE_FLAG_UNSORTED, OBJECTIVE_FLAG_SIZE, OBJECTIVE_FLAG_T_RANGE, OBJECTIVE_FLAG_EMPTY = 1, 2, 4, 8
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -181,10 +194,10 @@ def load_ops() -> C.CDLL:
     if not os.path.exists(OPS_LIB_PATH):
         raise RuntimeError(f"{OPS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
     lib = C.CDLL(OPS_LIB_PATH)
-    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(GCP2_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()):
+    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(GCP2_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = sig
-        fn.restype = {**MP_TRAIN_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES}.get(name, C.c_int)
+        fn.restype = {**MP_TRAIN_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES}.get(name, C.c_int)
     _ops_lib = lib
     return lib
 

@@ -158,7 +158,38 @@ class _MoleculeGenerationDDPM(nn.Module):
         with torch.inference_mode():
             return self._forward_impl(batch, dtype, t_int, noise)
 
+    def set_objective_path(self, path: str) -> None:
+        """"operators" (default) | "fused": EquivariantVariationalDiffusion.set_objective_path, plus the centring of x and the NLL assembled
+        from the terms (the tail of ``forward``) inside the same launches."""
+        self.ddpm.set_objective_path(path)
+
+    @property
+    def objective_path(self) -> str:
+        return self.ddpm.objective_path
+
+    def _forward_fused(self, batch, dtype, t_int, noise):
+        """``_forward_impl`` on the fused objective: x is centred, the terms are weighted and averaged inside its launches.  No device-to-host
+        copy when ``batch.num_graphs`` is given; ``batch.x`` is left as it came.  ``loss_info["loss"]`` = mean(nll) with the graph."""
+        batch.h = {"categorical": batch.one_hot, "integer": batch.charges}
+        ctx = getattr(batch, "props_context", None)
+        if self.condition_on_context:
+            if ctx is None:
+                raise ValueError("conditional model: batch.props_context (per node, normalised like the training set's) is required")
+            batch.props_context = ctx.type(dtype)
+        else:
+            batch.props_context = None
+        by_max = bool(cfg_get(self._init_kwargs["diffusion_cfg"], "norm_training_by_max_nodes", False))
+        out = self.ddpm(batch, return_loss_info=True, t_int=t_int, noise=noise, _objective=dict(center_x=True, norm_by_max_nodes=by_max))
+        nll, loss, means = self.ddpm.last_objective
+        loss_info = dict(out[-1])
+        for name in ("loss_t", "SNR_weight", "loss_0", "kl_prior", "delta_log_px", "neg_log_const_0", "log_pN"):
+            loss_info[name] = means[name]
+        loss_info["loss"] = loss
+        return nll, loss_info
+
     def _forward_impl(self, batch, dtype, t_int, noise):
+        if self.ddpm.objective_path == "fused":
+            return self._forward_fused(batch, dtype, t_int, noise)
         bi, mask = batch.batch, batch.mask
         B = int(bi.max().item()) + 1
         batch.x = _segment_mean_sub(batch.x, bi, B, mask)                         # centralize(..., edm=True): translation-invariant positions
@@ -197,8 +228,9 @@ class _MoleculeGenerationDDPM(nn.Module):
         if not self.training:
             raise RuntimeError("training_step needs .train() (evaluation mode scores the NLL without gradients)")
         nll, metrics = self.step(batch, **kw)
+        loss = metrics.pop("loss", None)                       # the fused objective's own mean(nll), with the graph
         metrics = {k: v.detach() for k, v in metrics.items()}
-        metrics["loss"] = nll.mean(0)
+        metrics["loss"] = nll.mean(0) if loss is None else loss
         return metrics
 
     def step(self, batch: Any, **kw) -> Tuple[torch.Tensor, Dict[str, Any]]:
@@ -218,7 +250,8 @@ class _MoleculeGenerationDDPM(nn.Module):
     def validation_step(self, batch: Any, batch_idx: int = 0, **kw) -> Dict[str, Any]:
         """The metrics dictionary of the reference's validation / test step (without the Lightning logging around it)."""
         nll, metrics = self.step(batch, **kw)
-        metrics["loss"] = nll.mean(0)
+        if "loss" not in metrics:                              # (the fused objective brings its own mean(nll))
+            metrics["loss"] = nll.mean(0)
         g = self.ddpm.gamma.gamma
         metrics["log_SNR_max"], metrics["log_SNR_min"] = -g[0], -g[-1]            # -gamma(0), -gamma(1)
         return metrics

@@ -748,3 +748,145 @@ def gcp2_fused(s: torch.Tensor, v: torch.Tensor, F: torch.Tensor, weights, SO: i
     weights = list(weights)
     record = torch.is_grad_enabled() and any(t.requires_grad for t in (s, v, *weights))
     return _GCP2Fused.apply(s, v, F, row_mask, dims, record, *weights)
+
+
+# ---- the diffusion objective around the network evaluation (include/gcdm_objective.h) ----------------------------------------------------------
+OBJECTIVE_TERMS = ("delta_log_px", "error_t", "SNR_weight", "loss_0_x", "loss_0_h", "neg_log_constants", "kl_prior", "log_pN", "eps_hat_x", "eps_hat_h")
+OBJECTIVE_MEANS = ("loss", "loss_t", "SNR_weight", "loss_0", "kl_prior", "delta_log_px", "neg_log_const_0", "log_pN", "eps_hat_x", "eps_hat_h")
+
+
+def objective_workspace_bytes(N: int, B: int, D: int, mode: int) -> int:
+    n = int(_lib().gcdm_objective_workspace_bytes(int(N), int(B), int(D), int(mode)))
+    if n < 0:
+        raise ValueError(f"gcdm_objective_workspace_bytes({N}, {B}, {D}, {mode}): bad argument")
+    return n
+
+
+class ObjectiveState:
+    """What gcdm_objective_prepare wrote for one batch (xh, eps_t, z_t, t_node, mol [B, 8]; eps_0, z_0 in evaluation mode) together with
+    the inputs the later entries read again.  ``read_flags()`` copies the device flag word to the host (the one sync; call it when convenient),
+    clears it and raises for what it says."""
+
+    def read_flags(self) -> int:
+        fl = int(self.flags.item())
+        if fl:
+            self.flags.zero_()
+        if fl & _native.OBJECTIVE_FLAG_UNSORTED:
+            raise ValueError("diffusion_objective: batch_index must be non-decreasing (molecules contiguous in node order)")
+        if fl & _native.OBJECTIVE_FLAG_T_RANGE:
+            raise ValueError(f"diffusion_objective: t_int outside 0 .. {self.T}")
+        if fl & _native.OBJECTIVE_FLAG_EMPTY:
+            raise ValueError("diffusion_objective: a molecule has no unmasked node")
+        if fl & _native.OBJECTIVE_FLAG_SIZE:
+            raise KeyError("diffusion_objective: a molecule's size is missing from the histogram of NumNodesDistribution (its log_pN is NaN)")
+        return fl
+
+
+def objective_prepare(x: torch.Tensor, one_hot: torch.Tensor, charges: Optional[torch.Tensor], mask: Optional[torch.Tensor],
+                      batch_index: torch.Tensor, num_graphs: int, t_int: torch.Tensor, gamma: torch.Tensor, log_pn: torch.Tensor, norm_values,
+                      norm_biases, eps_raw: torch.Tensor, eps_raw_0: Optional[torch.Tensor], num_atom_types: int, include_charges: bool, T: int,
+                      mode: int, flags: torch.Tensor, center_x: bool = False) -> ObjectiveState:
+    """Two launches: gcdm_op_rowptr (node_offsets from ``batch_index``) and gcdm_objective_prepare; plus one conversion launch when ``t_int``
+    is not int32 already.  ``flags``: an int32 [1] device tensor the caller keeps (OR-ed into, read lazily with ``state.read_flags()``)."""
+    nf, ic, B = int(num_atom_types), int(bool(include_charges)), int(num_graphs)
+    D = 3 + nf + ic
+    N = int(x.shape[0])
+    _shape(x.dim() == 2 and x.shape[1] == 3 and N >= 1 and 1 <= B <= N, f"diffusion_objective: x {tuple(x.shape)} must be [N, 3] with 1 <= B = {B} <= N")
+    _shape(1 <= nf <= _native.OBJECTIVE_MAX_TYPES and N * D < 2 ** 31, f"diffusion_objective: {nf} atom types (1 .. {_native.OBJECTIVE_MAX_TYPES}), N * D < 2^31")
+    _shape(tuple(one_hot.shape) == (N, nf), f"diffusion_objective: one_hot {tuple(one_hot.shape)} must be [{N}, {nf}]")
+    _shape(not ic or (charges is not None and charges.numel() == N), "diffusion_objective: charges must have one entry per node")
+    _shape(batch_index.numel() == N and (mask is None or mask.numel() == N), "diffusion_objective: batch_index / mask must have one entry per node")
+    _shape(t_int.numel() == B and gamma.numel() == int(T) + 1 and log_pn.numel() >= 1, "diffusion_objective: t_int [B], gamma [T + 1], log_pn")
+    _shape(tuple(eps_raw.shape) == (N, D) and (eps_raw_0 is None or tuple(eps_raw_0.shape) == (N, D)), f"diffusion_objective: the raw draws must be [{N}, {D}]")
+    _shape(mode in (0, 1, 2) and (mode != _native.OBJECTIVE_EVAL or eps_raw_0 is not None), "diffusion_objective: mode / second draw")
+    _shape(flags.dtype == torch.int32 and flags.numel() == 1, "diffusion_objective: flags must be int32 [1]")
+    st = ObjectiveState()
+    xs, oh, er = _f(x), _f(one_hot), _f(eps_raw)
+    for t in (batch_index, t_int, gamma, log_pn, flags):
+        _dev(t)
+    ch = _f(charges).reshape(-1) if ic else None
+    e0 = _f(eps_raw_0) if mode == _native.OBJECTIVE_EVAL else None
+    bi = batch_index.reshape(-1).to(torch.int64).contiguous()
+    mk = None
+    if mask is not None:
+        _dev(mask)
+        mk = mask.reshape(-1).contiguous()
+        mk = mk.view(torch.uint8) if mk.dtype == torch.bool else mk.ne(0).view(torch.uint8)
+    ti = t_int.reshape(-1).to(torch.int32).contiguous()            # the conversion launch (torch.randint draws int64)
+    dev = xs.device
+    off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    _chk(_lib().gcdm_op_rowptr(_p(bi), N, B, _p(off), _p(flags), _st(xs)), "gcdm_op_rowptr")
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)          # noqa: E731
+    st.xh, st.eps_t, st.z_t, st.t_node, st.mol = new(N, D), new(N, D), new(N, D), new(N), new(B, 8)
+    st.eps_0, st.z_0 = (new(N, D), new(N, D)) if e0 is not None else (None, None)
+    st.nv, st.nb = (C.c_float * 3)(*[float(v) for v in norm_values]), (C.c_float * 3)(*[float(v) for v in norm_biases])
+    st.gamma, st.log_pn = _f(gamma).reshape(-1), _f(log_pn).reshape(-1)
+    _chk(_lib().gcdm_objective_prepare(_p(xs), _p(oh), _p(ch), _p(mk), _p(off), _p(ti), _p(st.gamma), _p(st.log_pn), st.log_pn.numel(), st.nv, st.nb,
+                                       _p(er), _p(e0), _p(st.xh), _p(st.eps_t), _p(st.z_t), _p(st.eps_0), _p(st.z_0), _p(st.t_node), _p(st.mol),
+                                       _p(flags), N, B, nf, ic, int(T), int(mode), int(bool(center_x)), _st(xs)), "gcdm_objective_prepare")
+    st.off, st.mask, st.flags, st.t_int = off, mk, flags, ti
+    st.N, st.B, st.D, st.nf, st.ic, st.T, st.mode = N, B, D, nf, ic, int(T), int(mode)
+    st.keep = (xs, oh, ch, er, e0, bi)
+    return st
+
+
+class _DiffusionObjective(torch.autograd.Function):
+    """gcdm_objective_terms + gcdm_objective_reduce forward, gcdm_objective_bwd backward; the only differentiable input is net_out."""
+
+    @staticmethod
+    def forward(ctx, net_out, st, net_out_0, norm_by_max_nodes):
+        N, B, D = st.N, st.B, st.D
+        _shape(tuple(net_out.shape) == (N, D) and (net_out_0 is None or tuple(net_out_0.shape) == (N, D)), f"diffusion_objective: net_out must be [{N}, {D}]")
+        _shape(st.mode != _native.OBJECTIVE_EVAL or net_out_0 is not None, "diffusion_objective: evaluation mode needs net_out_0")
+        no = _f(net_out)
+        n0 = _f(net_out_0) if st.mode == _native.OBJECTIVE_EVAL else None
+        dev = no.device
+        terms = torch.empty((B, 10), dtype=torch.float32, device=dev)
+        nll = torch.empty(B, dtype=torch.float32, device=dev)
+        means = torch.empty(16, dtype=torch.float32, device=dev)
+        ws = torch.empty(objective_workspace_bytes(N, B, D, st.mode), dtype=torch.uint8, device=dev)
+        _chk(_lib().gcdm_objective_terms(_p(no), _p(n0), _p(st.xh), _p(st.eps_t), _p(st.z_t), _p(st.eps_0), _p(st.z_0), _p(st.mask), _p(st.off),
+                                         _p(st.mol), _p(st.gamma), st.nv, st.nb, _p(terms), N, B, st.nf, st.ic, st.T, st.mode, _st(no)),
+             "gcdm_objective_terms")
+        _chk(_lib().gcdm_objective_reduce(_p(st.mol), _p(terms), _p(ws), _p(nll), _p(means), B, D, st.T, st.mode, int(bool(norm_by_max_nodes)), _st(no)),
+             "gcdm_objective_reduce")
+        ctx.st, ctx.no, ctx.ws = st, no, ws
+        ctx.set_materialize_grads(False)
+        st.terms_block, st.means_block = terms, means            # the columns without a gradient are read from here
+        return terms[:, 1], terms[:, 3], nll, means[0]
+
+    @staticmethod
+    def backward(ctx, g_err, g_l0x, g_nll, g_loss):
+        if torch.is_grad_enabled():
+            raise RuntimeError("diffusion_objective (fused objective path): double backward (create_graph=True) is not supported; use the operator path")
+        st = ctx.st
+        if st.mode == _native.OBJECTIVE_EVAL:
+            raise RuntimeError("diffusion_objective: the evaluation-mode objective has no backward")
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+
+        def vec(g):
+            if g is None:
+                return None, 0
+            g = g.detach()
+            if g.dtype != torch.float32 or g.dim() != 1 or g.stride(0) < 0:
+                g = g.to(torch.float32).reshape(-1).contiguous()
+            return g, int(g.stride(0))
+
+        (ge, se), (g0, s0), (gn, sn) = vec(g_err), vec(g_l0x), vec(g_nll)
+        gl = None if g_loss is None else g_loss.detach().to(torch.float32).reshape(1)
+        d = torch.empty((st.N, st.D), dtype=torch.float32, device=ctx.no.device)
+        _chk(_lib().gcdm_objective_bwd(_p(ge), se, _p(g0), s0, _p(gn), sn, _p(gl), _p(ctx.no), _p(st.eps_t), _p(st.mask), _p(st.off), _p(st.mol),
+                                       _p(ctx.ws), _p(d), st.N, st.B, st.D, st.mode, _st(d)), "gcdm_objective_bwd")
+        return d, None, None, None
+
+
+def diffusion_objective(net_out: torch.Tensor, state: ObjectiveState, net_out_0: Optional[torch.Tensor] = None, norm_by_max_nodes: bool = False):
+    """The loss terms of one batch from the network's output as one autograd node (two launches forward, one backward; d net_out is the only
+    gradient).  -> (terms, nll [B], loss, means): ``terms`` maps OBJECTIVE_TERMS to [B] tensors (error_t and loss_0_x carry the graph),
+    ``loss`` = mean(nll) carries it too, ``means`` maps OBJECTIVE_MEANS to detached scalars (the batch means ``loss_info`` reports)."""
+    error_t, loss_0_x, nll, loss = _DiffusionObjective.apply(net_out, state, net_out_0, bool(norm_by_max_nodes))
+    tb, mb = state.terms_block, state.means_block
+    terms = {k: tb[:, i] for i, k in enumerate(OBJECTIVE_TERMS)}
+    terms["error_t"], terms["loss_0_x"] = error_t, loss_0_x
+    return terms, nll, loss, {k: mb[i] for i, k in enumerate(OBJECTIVE_MEANS)}

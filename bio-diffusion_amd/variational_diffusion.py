@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _native
+from . import _native, ops
 from .config import AttrDict, cfg_get
 from .gcpnet import F16RangeError
 
@@ -307,6 +307,9 @@ class EquivariantVariationalDiffusion(nn.Module):
         self.gamma = PredefinedNoiseSchedule(noise_schedule=cfg_get(diffusion_cfg, "noise_schedule"), num_timesteps=self.T,
                                              noise_precision=float(cfg_get(diffusion_cfg, "noise_precision")))
         self._gamma_uploaded = None
+        self._objective_path = "operators"
+        self._objective_flags = None          # int32 [1] on the device, OR-ed into by the fused objective, read lazily (read_objective_flags)
+        self._log_pn_cache = None
         # outcome of the last sampling call: device flag word, range rewinds, step an fp32 resume started from
         self.last_flags, self.last_range_rewinds, self.last_range_resume_step = 0, 0, None
 
@@ -450,8 +453,119 @@ class EquivariantVariationalDiffusion(nn.Module):
             log_ph = log_ph + psum(mass(h_int - (z_0[:, -1:] * nv[2] + nb[2]), sigma_0 * nv[2]) * m)
         return log_px, log_ph
 
+    # ---- how the objective around the network evaluation runs -------------------------------------------------------------------
+    def why_not_fused_objective(self, batch=None) -> Optional[str]:
+        """The first reason the fused objective (include/gcdm_objective.h) cannot serve this configuration / batch, or None."""
+        if self.diffusion_target != "atom_types_and_coords":
+            return f"diffusion_target={self.diffusion_target!r}: only 'atom_types_and_coords' is built"
+        if bool(cfg_get(self.diffusion_cfg, "generate_x_only", False)):
+            return "generate_x_only: the fused objective scores positions and node features together"
+        if self.num_x_dims != 3 or not 1 <= self.num_atom_types <= _native.OBJECTIVE_MAX_TYPES:
+            return f"num_x_dims={self.num_x_dims}, num_atom_types={self.num_atom_types}: 3 and 1 .. {_native.OBJECTIVE_MAX_TYPES} are built"
+        if batch is not None:
+            for name in ("x", "batch", "mask"):
+                t = cfg_get(batch, name)
+                if isinstance(t, torch.Tensor) and t.device.type != "cuda":
+                    return f"a CPU tensor (batch.{name} is on {t.device}): the fused objective runs on an MI355X only"
+        return None
+
+    def set_objective_path(self, path: str) -> None:
+        """"operators" (default) | "fused": how everything in ``forward`` outside ``dynamics_network(...)`` runs.  "fused" = the noising and
+        the per-molecule terms that need no network in one launch, the loss terms and their reduction as one autograd node whose backward is
+        one launch (ops.diffusion_objective, include/gcdm_objective.h); raises NotImplementedError naming the first reason when the
+        configuration is outside what the kernels implement.  The raw draws stay torch's, in the operator path's order."""
+        if path not in ("operators", "fused"):
+            raise ValueError(f"objective path must be 'operators' or 'fused', got {path!r}")
+        if path == "fused":
+            why = self.why_not_fused_objective()
+            if why is not None:
+                raise NotImplementedError(f"objective path 'fused': the fused objective does not implement this configuration ({why})")
+        self._objective_path = path
+
+    @property
+    def objective_path(self) -> str:
+        return self._objective_path
+
+    def read_objective_flags(self) -> int:
+        """The device flag word of the fused objective since the last read (one host sync; call it when convenient, e.g. once per logging
+        interval).  Raises what the operator path raises on the spot: ValueError for an unsorted batch index, KeyError for a molecule size
+        the histogram does not have."""
+        if self._objective_flags is None:
+            return 0
+        st = ops.ObjectiveState()
+        st.flags, st.T = self._objective_flags, self.T
+        return st.read_flags()
+
+    def _log_pn_table(self, dev) -> torch.Tensor:
+        """log p(N) indexed by molecule size on the device, NaN where the histogram has no entry; rebuilt when the buffer changes."""
+        nd = self.num_nodes_distribution
+        key = (str(dev), nd.prob.data_ptr(), _native.tensor_version(nd.prob))
+        if self._log_pn_cache is None or self._log_pn_cache[0] != key:
+            tab = torch.full((max(nd.keys) + 2,), float("nan"), dtype=torch.float32, device=dev)
+            tab[nd.num_nodes.to(dev)] = torch.log(nd.prob + nd.eps).to(dev, torch.float32)
+            self._log_pn_cache = (key, tab)
+        return self._log_pn_cache[1]
+
+    def _fused_loss_terms(self, batch, return_loss_info, t_int, noise, self_conditioning_prob, fix_self_conditioning_noise,
+                          center_x: bool = False, norm_by_max_nodes: bool = False):
+        """``_loss_terms`` on the fused objective: same draws in the same order, same tuple.  ``self.last_objective`` keeps (nll, loss, means)
+        for the module that assembles the NLL (``center_x`` / ``norm_by_max_nodes`` are its two switches)."""
+        training = self.training
+        l2 = training and cfg_get(self.diffusion_cfg, "loss_type", "l2") == "l2"
+        mode = _native.OBJECTIVE_EVAL if not training else (_native.OBJECTIVE_TRAIN_L2 if l2 else _native.OBJECTIVE_TRAIN_VLB)
+        bi, mask, x = batch.batch, batch.mask, batch.x
+        dev, N = x.device, int(x.shape[0])
+        ng = cfg_get(batch, "num_graphs")
+        B = int(bi.max().item()) + 1 if ng is None else int(ng)
+        if t_int is None:
+            t_int = torch.randint(0 if training else 1, self.T + 1, size=(B, 1), device=dev)
+        t_int = t_int.to(dev).reshape(B, 1)
+        F_ = self.num_node_scalar_features
+
+        def raw(k):
+            if noise is not None:
+                return noise[k].to(dev)
+            return torch.cat([torch.randn((N, self.num_x_dims), device=dev), torch.randn((N, F_), device=dev)], dim=-1)
+
+        eps_raw = raw(0)
+        eps_raw_0 = None if training else raw(1)
+        if self._objective_flags is None or self._objective_flags.device != dev:
+            self._objective_flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        nv, nb = cfg_get(self.diffusion_cfg, "norm_values"), cfg_get(self.diffusion_cfg, "norm_biases")
+        st = ops.objective_prepare(x, batch.h["categorical"], batch.h["integer"] if self.include_charges else None, mask, bi, B, t_int,
+                                   self.gamma.gamma, self._log_pn_table(dev), [float(v) for v in nv], [0.0 if v is None else float(v) for v in nb],
+                                   eps_raw, eps_raw_0, self.num_atom_types, self.include_charges, self.T, mode, self._objective_flags,
+                                   center_x=center_x)
+        t_node = st.t_node.view(N, 1)
+        net_out_0 = None
+        if training:
+            self_cond = None
+            if bool(cfg_get(self.diffusion_cfg, "self_condition", False)) and not bool((t_int == self.T).any()) and _random() < self_conditioning_prob:
+                with torch.no_grad():                       # the estimate the network is conditioned on stays on the operator path
+                    t_sc = (t_int + 1) / self.T
+                    z_sc, _ = self.compute_noised_representation(st.xh, bi, mask, inflate_batch_array(self.gamma(t_sc), x))
+                    self_cond = self.sample_p_zs_given_zt(s=torch.zeros_like(t_sc), t=t_sc, z=z_sc, batch_index=bi, node_mask=mask,
+                                                          context=getattr(batch, "props_context", None), fix_noise=fix_self_conditioning_noise,
+                                                          self_condition=True).detach()
+            _, net_out = self.dynamics_network(batch, st.z_t, t_node, xh_self_cond=self_cond)
+        else:
+            t_zeros = torch.zeros((N, 1), dtype=torch.float32, device=dev)
+
+            def two_evaluations():
+                a = self.dynamics_network(batch, st.z_t, t_node, xh_self_cond=None, **self._deferred())[1]
+                b = self.dynamics_network(batch, st.z_0, t_zeros, xh_self_cond=None, **self._deferred())[1]
+                self._final_range_check()
+                return a, b
+            net_out, net_out_0 = self._rerun_in_fp32(two_evaluations, "the network evaluations")
+        terms, nll, loss, means = ops.diffusion_objective(net_out, st, net_out_0, norm_by_max_nodes=norm_by_max_nodes)
+        self.last_objective = (nll, loss, means)
+        out = tuple(terms[k] for k in ops.OBJECTIVE_TERMS[:8]) + (t_int.squeeze(-1),)
+        if not return_loss_info:
+            return out
+        return (*out, {"eps_hat_x": means["eps_hat_x"], "eps_hat_h": means["eps_hat_h"]})
+
     def forward(self, batch, return_loss_info: bool = False, t_int: Optional[torch.Tensor] = None, noise: Optional[List[torch.Tensor]] = None,
-                self_conditioning_prob: float = 0.5, fix_self_conditioning_noise: bool = False):
+                self_conditioning_prob: float = 0.5, fix_self_conditioning_noise: bool = False, _objective: Optional[Dict[str, Any]] = None):
         """Loss / NLL terms of a data batch (:948-1160): (delta_log_px, error_t, SNR_weight, loss_0_x, loss_0_h, neg_log_constants, kl_prior,
         log_pN, t_int[, loss_info]), each per molecule.  ``batch``: x (CoM-free), h = {categorical, integer}, batch, mask, num_graphs,
         num_nodes_present, props_context (per node or None).
@@ -462,10 +576,16 @@ class EquivariantVariationalDiffusion(nn.Module):
         [N, 3 + F] (evaluation: two, for z_t and z_0; training: one)."""
         if self.diffusion_target != "atom_types_and_coords":
             raise NotImplementedError(f"diffusion_target {self.diffusion_target!r}")
+        fn = self._loss_terms
+        if self._objective_path == "fused":
+            why = self.why_not_fused_objective(batch)
+            if why is not None:
+                raise NotImplementedError(f"objective path 'fused': {why}")
+            fn = lambda *a: self._fused_loss_terms(*a, **(_objective or {}))          # noqa: E731
         if self.training:
-            return self._loss_terms(batch, return_loss_info, t_int, noise, self_conditioning_prob, fix_self_conditioning_noise)
+            return fn(batch, return_loss_info, t_int, noise, self_conditioning_prob, fix_self_conditioning_noise)
         with torch.inference_mode():
-            return self._loss_terms(batch, return_loss_info, t_int, noise, self_conditioning_prob, fix_self_conditioning_noise)
+            return fn(batch, return_loss_info, t_int, noise, self_conditioning_prob, fix_self_conditioning_noise)
 
     def _loss_terms(self, batch, return_loss_info, t_int, noise, self_conditioning_prob, fix_self_conditioning_noise):
         training = self.training

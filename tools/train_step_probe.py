@@ -12,6 +12,9 @@ syncs, AdamW amsgrad, the per-entry EMA), `fused` optim.TrainingUpdate (three la
 --node-path fused runs every stand-alone GCP2 (the embedding GCPs, the feed-forward and position GCPs of each layer, the scalar projection) as
 one autograd node on the fused GCP2 kernels (GCPNetDynamics.set_node_path, include/gcdm_gcp2_train.h); independent of --message-path.
 
+--objective-path fused runs everything around the network evaluation -- noising, loss terms, their backward -- on the fused objective
+(EquivariantVariationalDiffusion.set_objective_path, include/gcdm_objective.h): four launches forward, one backward; independent of the others.
+
 The step is bench.py's `training_step`: forward in training mode + loss + backward of one 64-molecule QM9 batch through libgcdm_ops.so's operators."""
 import importlib
 import os
@@ -47,7 +50,7 @@ def _torch_update(params):
     return step
 
 
-def build_step(message_path="operators", update="none", node_path="operators"):
+def build_step(message_path="operators", update="none", node_path="operators", objective_path="operators"):
     import synth
     pkg = importlib.import_module("bio-diffusion_amd")
     dev = torch.device("cuda", 0)
@@ -65,6 +68,7 @@ def build_step(message_path="operators", update="none", node_path="operators"):
     info = pkg.dataset_info("qm9")
     ddpm = pkg.EquivariantVariationalDiffusion(net, cfgs["diffusion_cfg"], cfgs["dataloader_cfg"], info).to(dev)
     ddpm._native(dev)
+    ddpm.set_objective_path(objective_path)
     Bt, n = 64, 19
     nt_ = torch.full((Bt,), n, dtype=torch.long, device=dev)
     Nt = Bt * n
@@ -101,10 +105,11 @@ def main():
     ap.add_argument("steps", nargs="?", type=int, default=10)
     ap.add_argument("--message-path", choices=("operators", "fused"), default="operators")
     ap.add_argument("--node-path", choices=("operators", "fused"), default="operators")
+    ap.add_argument("--objective-path", choices=("operators", "fused"), default="operators")
     ap.add_argument("--update", choices=("none", "torch", "fused"), default="none")
     args = ap.parse_args()
     steps = args.steps
-    once, dev = build_step(args.message_path, args.update, args.node_path)
+    once, dev = build_step(args.message_path, args.update, args.node_path, args.objective_path)
     for _ in range(3):
         once()
     torch.cuda.synchronize(dev)
@@ -117,7 +122,7 @@ def main():
     t_host = (time.perf_counter() - t0) / steps * 1e3          # host done enqueueing
     torch.cuda.synchronize(dev)
     wall = (time.perf_counter() - t0) / steps * 1e3
-    print(f"training step, 64 x 19, message path {args.message_path}, node path {args.node_path}, update {args.update}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
+    print(f"training step, 64 x 19, message path {args.message_path}, node path {args.node_path}, objective path {args.objective_path}, update {args.update}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
 
 
 if __name__ == "__main__":
