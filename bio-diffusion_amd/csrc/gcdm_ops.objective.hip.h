@@ -184,8 +184,8 @@ __global__ void __launch_bounds__(THREADS) k_obj_terms(TermArgs a) {
         }
         ax += sa_x / 3.f;
         ah += sa_h / (float)(D - 3);
+        err += re;                  // error_t sums over ALL rows as the reference does: the projection's output on a masked row is not zero
         if (!present) continue;
-        err += re;
         float r0 = 0.f;
         for (int j = 0; j < 3; ++j) { const float d = eps[base + j] - net[base + j]; r0 += d * d; }
         l0x += r0;
@@ -320,12 +320,9 @@ __global__ void __launch_bounds__(THREADS) k_obj_bwd(BwdArgs a) {
     for (int i = lane; i < n; i += 64) {
         const int r = o0 + i / D, j = i - (i / D) * D;
         const int64_t at = (int64_t)o0 * D + i;
-        float d = 0.f;
-        if (a.mask == nullptr || a.mask[r] != 0) {
-            const float df = a.eps_t[at] - a.net[at];
-            d = kt * df;
-            if (j < 3) d = d + k0 * df;
-        }
+        const float df = a.eps_t[at] - a.net[at];
+        float d = kt * df;
+        if (j < 3 && (a.mask == nullptr || a.mask[r] != 0)) d = d + k0 * df;
         a.d_net[at] = d;
     }
 }

@@ -147,16 +147,16 @@ class _MoleculeGenerationDDPM(nn.Module):
 
     # ---- loss / likelihood of a data batch (training, validation, test step), qm9_mol_gen_ddpm.py:184-277, 340-360, 429-459 --------
     def forward(self, batch: Any, dtype: torch.dtype = torch.float32, t_int: Optional[torch.Tensor] = None,
-                noise: Optional[List[torch.Tensor]] = None) -> Tuple[torch.Tensor, Dict[str, Any]]:
+                noise: Optional[List[torch.Tensor]] = None, self_conditioning_prob: float = 0.5) -> Tuple[torch.Tensor, Dict[str, Any]]:
         """Loss per molecule and the batch means of the monitored terms.  Evaluation mode: the NLL (two evaluations of the network, fused
         kernels, inference mode).  Training mode: the L2 or VLB objective of ``diffusion_cfg.loss_type`` with gradients -- the network runs on
         the module path (HIP operators with autograd).  ``batch``: x, one_hot, charges, batch, mask and -- for a conditional model -- the
         per-node ``props_context`` (the reference derives it from the training set's property statistics, qm9utils.prepare_context; that data
-        path is outside this package).  ``t_int`` / ``noise``: see EquivariantVariationalDiffusion.forward."""
+        path is outside this package).  ``t_int`` / ``noise`` / ``self_conditioning_prob``: see EquivariantVariationalDiffusion.forward."""
         if self.training:
-            return self._forward_impl(batch, dtype, t_int, noise)
+            return self._forward_impl(batch, dtype, t_int, noise, self_conditioning_prob)
         with torch.inference_mode():
-            return self._forward_impl(batch, dtype, t_int, noise)
+            return self._forward_impl(batch, dtype, t_int, noise, self_conditioning_prob)
 
     def set_objective_path(self, path: str) -> None:
         """"operators" (default) | "fused": EquivariantVariationalDiffusion.set_objective_path, plus the centring of x and the NLL assembled
@@ -167,7 +167,7 @@ class _MoleculeGenerationDDPM(nn.Module):
     def objective_path(self) -> str:
         return self.ddpm.objective_path
 
-    def _forward_fused(self, batch, dtype, t_int, noise):
+    def _forward_fused(self, batch, dtype, t_int, noise, self_conditioning_prob=0.5):
         """``_forward_impl`` on the fused objective: x is centred, the terms are weighted and averaged inside its launches.  No device-to-host
         copy when ``batch.num_graphs`` is given; ``batch.x`` is left as it came.  ``loss_info["loss"]`` = mean(nll) with the graph."""
         batch.h = {"categorical": batch.one_hot, "integer": batch.charges}
@@ -179,7 +179,8 @@ class _MoleculeGenerationDDPM(nn.Module):
         else:
             batch.props_context = None
         by_max = bool(cfg_get(self._init_kwargs["diffusion_cfg"], "norm_training_by_max_nodes", False))
-        out = self.ddpm(batch, return_loss_info=True, t_int=t_int, noise=noise, _objective=dict(center_x=True, norm_by_max_nodes=by_max))
+        out = self.ddpm(batch, return_loss_info=True, t_int=t_int, noise=noise, self_conditioning_prob=self_conditioning_prob,
+                        _objective=dict(center_x=True, norm_by_max_nodes=by_max))
         nll, loss, means = self.ddpm.last_objective
         loss_info = dict(out[-1])
         for name in ("loss_t", "SNR_weight", "loss_0", "kl_prior", "delta_log_px", "neg_log_const_0", "log_pN"):
@@ -187,9 +188,9 @@ class _MoleculeGenerationDDPM(nn.Module):
         loss_info["loss"] = loss
         return nll, loss_info
 
-    def _forward_impl(self, batch, dtype, t_int, noise):
+    def _forward_impl(self, batch, dtype, t_int, noise, self_conditioning_prob=0.5):
         if self.ddpm.objective_path == "fused":
-            return self._forward_fused(batch, dtype, t_int, noise)
+            return self._forward_fused(batch, dtype, t_int, noise, self_conditioning_prob)
         bi, mask = batch.batch, batch.mask
         B = int(bi.max().item()) + 1
         batch.x = _segment_mean_sub(batch.x, bi, B, mask)                         # centralize(..., edm=True): translation-invariant positions
@@ -204,7 +205,7 @@ class _MoleculeGenerationDDPM(nn.Module):
         num_nodes = torch.zeros(B, dtype=torch.long, device=bi.device).index_add_(0, bi, mask.long())
         batch.num_nodes_present, batch.num_graphs = num_nodes, B
         (delta_log_px, error_t, SNR_weight, loss_0_x, loss_0_h, neg_log_const_0, kl_prior, log_pN, t_int, loss_info) = self.ddpm(
-            batch, return_loss_info=True, t_int=t_int, noise=noise)
+            batch, return_loss_info=True, t_int=t_int, noise=noise, self_conditioning_prob=self_conditioning_prob)
         if self.training and cfg_get(self._init_kwargs["diffusion_cfg"], "loss_type", "l2") == "l2":
             # L2 training objective (:222-234): the squared error per predicted number, the x part of L_0 normalised the same way
             eff = num_nodes.max() if cfg_get(self._init_kwargs["diffusion_cfg"], "norm_training_by_max_nodes", False) else num_nodes

@@ -506,6 +506,11 @@ class EquivariantVariationalDiffusion(nn.Module):
             self._log_pn_cache = (key, tab)
         return self._log_pn_cache[1]
 
+    @staticmethod
+    def _sc_draw(noise, k, dev):
+        """Entry k of a three-entry training ``noise`` list (the two draws of the self-conditioning estimate), or None: torch.randn draws it."""
+        return noise[k].to(dev) if noise is not None and len(noise) > k else None
+
     def _fused_loss_terms(self, batch, return_loss_info, t_int, noise, self_conditioning_prob, fix_self_conditioning_noise,
                           center_x: bool = False, norm_by_max_nodes: bool = False):
         """``_loss_terms`` on the fused objective: same draws in the same order, same tuple.  ``self.last_objective`` keeps (nll, loss, means)
@@ -541,12 +546,12 @@ class EquivariantVariationalDiffusion(nn.Module):
         if training:
             self_cond = None
             if bool(cfg_get(self.diffusion_cfg, "self_condition", False)) and not bool((t_int == self.T).any()) and _random() < self_conditioning_prob:
-                with torch.no_grad():                       # the estimate the network is conditioned on stays on the operator path
+                with torch.no_grad():                       # the estimate: gradients off, so the network runs on the sampler's fused kernels
                     t_sc = (t_int + 1) / self.T
-                    z_sc, _ = self.compute_noised_representation(st.xh, bi, mask, inflate_batch_array(self.gamma(t_sc), x))
+                    z_sc, _ = self.compute_noised_representation(st.xh, bi, mask, inflate_batch_array(self.gamma(t_sc), x), eps=self._sc_draw(noise, 1, dev))
                     self_cond = self.sample_p_zs_given_zt(s=torch.zeros_like(t_sc), t=t_sc, z=z_sc, batch_index=bi, node_mask=mask,
                                                           context=getattr(batch, "props_context", None), fix_noise=fix_self_conditioning_noise,
-                                                          self_condition=True).detach()
+                                                          self_condition=True, noise=self._sc_draw(noise, 2, dev)).detach()
             _, net_out = self.dynamics_network(batch, st.z_t, t_node, xh_self_cond=self_cond)
         else:
             t_zeros = torch.zeros((N, 1), dtype=torch.float32, device=dev)
@@ -573,7 +578,9 @@ class EquivariantVariationalDiffusion(nn.Module):
           * TRAINING mode (``.train()``): one evaluation at t >= 0 on the module path (HIP operators with autograd), the t = 0 terms masked
             in as the reference does (:1078-1101); ``loss_type == "l2"`` drops the weights / constants (:978, 1050-1063).
         Extensions for reproducible runs: ``t_int`` [B, 1] instead of the torch.randint draw, ``noise`` = the raw standard-normal draws
-        [N, 3 + F] (evaluation: two, for z_t and z_0; training: one)."""
+        [N, 3 + F] (evaluation: two, for z_t and z_0; training: one, or three with self-conditioning -- ``noise[1]`` noises the z the
+        estimate's jump starts from, ``noise[2]`` is the jump's own draw, masked and CoM-projected by sample_p_zs_given_zt; with one entry the
+        two come from torch.randn as without the argument)."""
         if self.diffusion_target != "atom_types_and_coords":
             raise NotImplementedError(f"diffusion_target {self.diffusion_target!r}")
         fn = self._loss_terms
@@ -610,10 +617,10 @@ class EquivariantVariationalDiffusion(nn.Module):
             if bool(cfg_get(self.diffusion_cfg, "self_condition", False)) and not bool((t_int == self.T).any()) and _random() < self_conditioning_prob:
                 with torch.no_grad():                       # the estimate the network is conditioned on: a jump from t + 1 to 0 (:1016-1035)
                     t_sc = (t_int + 1) / self.T
-                    z_sc, _ = self.compute_noised_representation(xh, bi, mask, inflate_batch_array(self.gamma(t_sc), x))
+                    z_sc, _ = self.compute_noised_representation(xh, bi, mask, inflate_batch_array(self.gamma(t_sc), x), eps=self._sc_draw(noise, 1, dev))
                     self_cond = self.sample_p_zs_given_zt(s=torch.zeros_like(t_sc), t=t_sc, z=z_sc, batch_index=bi, node_mask=mask,
                                                           context=getattr(batch, "props_context", None), fix_noise=fix_self_conditioning_noise,
-                                                          self_condition=True).detach()
+                                                          self_condition=True, noise=self._sc_draw(noise, 2, dev)).detach()
             _, net_out = self.dynamics_network(batch, z_t, t[bi], xh_self_cond=self_cond)
             error_t = self.sum_node_features_except_batch((eps_t - net_out) ** 2, bi, B)
             if l2:

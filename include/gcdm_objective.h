@@ -46,15 +46,16 @@
  * gcdm_objective_terms -- one launch.  Reads net_out [N,D] (and net_out_0 [N,D] with GCDM_OBJECTIVE_EVAL) and what prepare wrote; writes
  *   terms [B][10] = 0 delta_log_px, 1 error_t, 2 SNR_weight, 3 loss_0_x, 4 loss_0_h, 5 neg_log_constants, 6 kl_prior, 7 log_pN,
  *   8 eps_hat_x, 9 eps_hat_h (the molecule's mean over ALL its rows of mean_j |net_out|, x columns / other columns).
- *     error_t   = sum over unmasked rows and all columns of (eps_t - net_out)^2
+ *     error_t   = sum over ALL rows and all columns of (eps_t - net_out)^2 (eps_t is zero on a masked row, net_out is not: the reference
+ *                 sums the squared output of its scalar projection there too, variational_diffusion.py:1052)
  *     loss_0_x  = 0.5 sum over unmasked rows of the x columns of (eps - net)^2
  *     loss_0_h  = -log p(h | z_0): per unmasked row, log(cdf((c + .5) / w) - cdf((c - .5) / w) + 1e-10) per atom type with c = z nv1 + nb1 - 1,
  *                 w = sigma_0 nv1, minus its logsumexp over the types, weighted by xh nv1 + nb1; plus, with charges, the same mass at
  *                 c = rint(xh nv2 + nb2) - (z nv2 + nb2), w = sigma_0 nv2
  *   training modes: (eps, net, z, sigma_0) = (eps_t, net_out, z_t, sigma_t); error_t is multiplied by 1 - t_is_zero, loss_0_x and loss_0_h by
  *   t_is_zero.  GCDM_OBJECTIVE_EVAL: (eps_0, net_out_0, z_0, sigma(gamma[0])), no t_is_zero factors.  GCDM_OBJECTIVE_TRAIN_L2 writes
- *   delta_log_px = neg_log_constants = 0 and SNR_weight = 1.  (The network's output is zero at masked rows, so the sums over unmasked rows
- *   are the torch path's sums over all rows.)
+ *   delta_log_px = neg_log_constants = 0 and SNR_weight = 1.  (The x columns of the network's output are zero at masked rows, so loss_0_x over
+ *   unmasked rows is the torch path's sum over all rows.)
  *
  * gcdm_objective_reduce -- one launch of one workgroup.  nll [B] = loss_t + loss_0 + kl_prior - delta_log_px - log_pN with
  *   GCDM_OBJECTIVE_TRAIN_L2: loss_t = 0.5 error_t / den, loss_0 = loss_0_x / den + loss_0_h, den = D * (norm_by_max_nodes ? max_b
@@ -66,8 +67,8 @@
  *   gradients of terms columns 1 and 3, of nll and of means[0]; each may be NULL (= zero).  The three [B] gradients are read at
  *   g[b * stride] with an element stride >= 0 (1 = dense, 0 = one value for every molecule: what the backward of a mean hands over).
  *   Rows outside every molecule (node_offsets that do not cover 0 .. N) are not written.  With G = g_nll_b + g_loss / B:
- *     d_net_out[i][j] = m_i ( -2 (1 - t_is_zero) (g_error_t_b + G ct_b) - [j < 3] t_is_zero (g_loss_0_x_b + G c0_b) ) (eps_t - net_out)[i][j]
- *   with (ct, c0) from `workspace`.  Masked rows get exactly 0. */
+ *     d_net_out[i][j] = ( -2 (1 - t_is_zero) (g_error_t_b + G ct_b) - m_i [j < 3] t_is_zero (g_loss_0_x_b + G c0_b) ) (eps_t - net_out)[i][j]
+ *   with (ct, c0) from `workspace`.  Masked rows get the error_t part only. */
 #ifndef GCDM_OBJECTIVE_H
 #define GCDM_OBJECTIVE_H
 #include <stdint.h>

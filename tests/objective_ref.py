@@ -152,7 +152,7 @@ def terms(net_out, net_out_0, prep, mask, off, gamma, nv, nb, nf, ic, T, mode, d
     sig0 = _sig(gamma.to(dtype)[0] if ev else mol[:, 7])
     sig0 = (sig0.expand(B) if sig0.dim() == 0 else sig0)[bi].unsqueeze(-1)
     xh = prep["xh"]
-    err = _seg((((prep["eps_t"] - no) ** 2) * mu).sum(-1), bi, B)
+    err = _seg(((prep["eps_t"] - no) ** 2).sum(-1), bi, B)          # over ALL rows, as the reference (tests/golden/train_full_qm9mask.npz)
     l0x = 0.5 * _seg((((eps[:, :3] - net[:, :3]) ** 2) * mu).sum(-1), bi, B)
     lp = _mass(z[:, 3:3 + nf] * nv[1] + nb[1] - 1.0, sig0 * nv[1], mutant)
     if mutant != "no_logsumexp":
@@ -222,8 +222,8 @@ def bwd(g_error_t, g_loss_0_x, g_nll, g_loss, net_out, eps_t, mask, off, mol, co
     m = torch.ones(len(bi), dtype=dtype) if mask is None else (mask != 0).to(dtype)
     df = eps_t.to(dtype) - net_out.to(dtype)
     d = (-2 * (1 - t0) * Gt)[bi].unsqueeze(-1) * df
-    d[:, :3] += (-(t0 * G0))[bi].unsqueeze(-1) * df[:, :3]
-    return d * m.unsqueeze(-1)
+    d[:, :3] += (-(t0 * G0))[bi].unsqueeze(-1) * df[:, :3] * m.unsqueeze(-1)
+    return d
 
 
 def run(inp, net_out, net_out_0=None, by_max=False, dtype=torch.float64, mutant=None):

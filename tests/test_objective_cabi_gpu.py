@@ -136,9 +136,12 @@ def _clear_of_epsilon(inp, r32):
 
 
 def _net(inp, seed=1):
+    """As the real network on masked rows: the x columns zero, the other columns not (the scalar projection's bias, gcpnet.py:1190)."""
     N, D = int(inp["off"][-1]), 3 + inp["nf"] + inp["ic"]
     g = torch.Generator().manual_seed(seed)
-    m = torch.ones(N, 1) if inp["mask"] is None else (inp["mask"] != 0).float().unsqueeze(-1)
+    m = torch.ones(N, D)
+    if inp["mask"] is not None:
+        m[:, :3] = (inp["mask"] != 0).float().unsqueeze(-1)
     return torch.randn((N, D), generator=g) * m, (torch.randn((N, D), generator=g) * m if inp["mode"] == R.EVAL else None)
 
 
@@ -173,7 +176,20 @@ def _check(inp, by_max=False, label="", with_bwd=True, M=4.0):
         d32, d64 = a(r32, torch.float32), a(r64, torch.float64)
         checks.append(("d_net_out", got["d"], d32, d64, 2 * d64.abs()))
         if inp["mask"] is not None:
-            assert (got["d"][~(inp["mask"] != 0).numpy()] == 0).all(), "masked rows must get exactly 0"
+            # masked rows get the error_t part only: exactly 0 where t = 0 selects loss_0_x, and elsewhere what a kernel that skips them
+            # (d = 0) would miss by far more than the bar below allows
+            gone, t0 = ~(inp["mask"] != 0), r64["prep"]["mol"][:, 4][R._bi(inp["off"])] == 1
+            assert (got["d"][(gone & t0).numpy()] == 0).all(), "masked rows of a t = 0 molecule must get exactly 0"
+            live = (gone & ~t0).numpy()
+            assert live.any() and (got["d"][live, :3] == 0).all()
+            want = d64[torch.from_numpy(live)][:, 3:]
+            assert want.abs().min().item() > 0 and np.abs(got["d"][live, 3:] - want.numpy()).max() <= 1e-4 * want.abs().max().item()
+    if inp["mask"] is not None:          # error_t over ALL rows: the sum over unmasked rows is far from what the device gives
+        skipped, _ = R.terms(net * (inp["mask"] != 0).float().unsqueeze(-1), net0, r64["prep"], inp["mask"], inp["off"], inp["gamma"], inp["nv"], inp["nb"],
+                             inp["nf"], inp["ic"], inp["T"], inp["mode"])
+        moved = (r64["terms"][:, 1] - skipped[:, 1]).abs()
+        sel = moved > 0
+        assert sel.any() and (np.abs(got["terms"][:, 1] - r64["terms"][:, 1].numpy())[sel.numpy()] <= 1e-3 * moved[sel].numpy()).all()
     bad = []
     for k, g_, a32, a64, mg in checks:
         ok, fac = R.bar_ok(torch.from_numpy(np.asarray(g_)).reshape(a64.shape), a32, a64, mg, M)

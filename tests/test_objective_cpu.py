@@ -131,7 +131,7 @@ class _Stub(torch.nn.Module):
 
 
 @pytest.mark.parametrize("case,mode,by_max", [("qm9", R.TRAIN_L2, False), ("qm9", R.TRAIN_L2, True), ("qm9", R.TRAIN_VLB, False), ("qm9", R.EVAL, False),
-                                              ("geom", R.TRAIN_L2, False), ("geom", R.EVAL, False)])
+                                              ("geom", R.TRAIN_L2, False), ("geom", R.EVAL, False), ("qm9", R.TRAIN_VLB, True), ("geom", R.TRAIN_VLB, True)])
 def test_restatement_matches_the_packages_own_loss_terms_on_cpu_tensors(case, mode, by_max):
     """_loss_terms + the tail of _forward_impl in fp32 on the CPU (a stub network) against the fp32 restatement: 2e-5 relative, and the
     restatement's fp64 run within the same of both.  A mask with absent nodes; t_int holds 0, 1 and T."""
@@ -144,8 +144,10 @@ def test_restatement_matches_the_packages_own_loss_terms_on_cpu_tensors(case, mo
     inp = make_inputs(case, nn_, t_int, mode, seed=11, mask=mask, ddpm=ddpm)
     D = 3 + inp["nf"] + inp["ic"]
     g = torch.Generator().manual_seed(5)
-    net = torch.randn((N, D), generator=g) * mask.float().unsqueeze(-1)
-    net0 = torch.randn((N, D), generator=g) * mask.float().unsqueeze(-1) if mode == R.EVAL else None
+    keep = torch.ones(N, D)          # as the real network on masked rows: x columns zero, the other columns not (gcpnet.py:1190)
+    keep[:, :3] = mask.float().unsqueeze(-1)
+    net = torch.randn((N, D), generator=g) * keep
+    net0 = torch.randn((N, D), generator=g) * keep if mode == R.EVAL else None
     ddpm.dynamics_network = _Stub([net] if net0 is None else [net, net0])
     ddpm.train(mode != R.EVAL)
     bi = R._bi(inp["off"])
@@ -155,6 +157,9 @@ def test_restatement_matches_the_packages_own_loss_terms_on_cpu_tensors(case, mo
     out = ddpm(batch, return_loss_info=True, t_int=inp["t_int"].long().view(-1, 1), noise=[inp["eps_raw"], inp["eps_raw_0"]])
     r32, _ = R.run(inp, net, net0, by_max, torch.float32)
     r64, _ = R.run(inp, net, net0, by_max, torch.float64)
+    over_unmasked, _ = R.run(inp, net * mask.float().unsqueeze(-1), net0, by_max, torch.float64)
+    moved = (r64["terms"][:, 1] - over_unmasked["terms"][:, 1]).abs()
+    assert moved.max().item() > 1e-2 * r64["terms"][:, 1].abs().max().item(), "the masked rows must carry weight in error_t"
     for i, name in enumerate(TRAIN_TERMS):
         for r in (r32, r64):
             err = (out[i].detach().double() - r["terms"][:, i].double()).abs().max().item()
@@ -191,7 +196,9 @@ def test_closed_form_gradient_equals_autograd_through_the_restatement(mode, by_m
     ((tr[:, 1] * ge).sum() + (tr[:, 3] * g0).sum() + (nll * gn).sum() + means[0] * gl).backward()
     want = R.bwd(ge, g0, gn, gl, net.detach(), prep["eps_t"], mask, inp["off"], prep["mol"], coef.detach())
     assert (net.grad - want).abs().max().item() <= 1e-12 * max(1.0, want.abs().max().item())
-    assert (want[~mask] == 0).all() and want[mask].abs().max().item() > 0
+    # masked rows carry the error_t part (the reference sums error_t over all rows), never the loss_0_x part
+    t0 = prep["mol"][:, 4][R._bi(inp["off"])]
+    assert (want[~mask][t0[~mask] == 1] == 0).all() and want[~mask].abs().max().item() > 0 and want[mask].abs().max().item() > 0
 
 
 def _mutant_case(mutant):
@@ -225,6 +232,91 @@ def test_the_bar_rejects_each_mutant_of_the_fp32_emulation(mutant):
     inp, net, net0 = _mutant_case(mutant)
     assert not any(_rejected(inp, net, net0, None)), "the unmutated fp32 run must pass its own bar"
     assert any(_rejected(inp, net, net0, mutant)), mutant
+
+
+class _Recorder(torch.nn.Module):
+    """A stub network with one parameter that records what it is called with."""
+
+    def __init__(self, N, D):
+        super().__init__()
+        self.w = torch.nn.Parameter(torch.ones(()))
+        self.calls, self.N, self.D = [], N, D
+
+    def forward(self, batch, z, t, **kw):
+        self.calls.append(dict(z=z, t=t, grad=torch.is_grad_enabled(), **kw))
+        return None, self.w * torch.full((self.N, self.D), 0.25)
+
+
+@pytest.mark.parametrize("entries", [3, 1, 0])
+def test_three_entry_noise_list_reaches_both_self_conditioning_draws(entries, monkeypatch):
+    """noise[1] is the eps= of the compute_noised_representation call that makes z_sc, noise[2] the raw noise= of sample_p_zs_given_zt; with
+    one entry or none the torch.randn calls are those of the code before the extension: (x, h) per missing draw, in order."""
+    ddpm, _ = _ddpm("qm9", self_condition=True)
+    nn_ = torch.tensor([4, 3])
+    N, D = int(nn_.sum()), 9
+    inp = make_inputs("qm9", nn_, [7, 999], R.TRAIN_L2, seed=1, ddpm=ddpm)
+    bi = R._bi(inp["off"])
+    mask = torch.ones(N, dtype=torch.bool)
+    net = _Recorder(N, D)
+    ddpm.dynamics_network = net
+    ddpm.train()
+    g = torch.Generator().manual_seed(8)
+    draws = [torch.randn((N, D), generator=g) for _ in range(3)]
+    seen = {}
+
+    def fake_jump(s, t, z, batch_index, node_mask, **kw):
+        seen.update(s=s, t=t, z=z, grad=torch.is_grad_enabled(), **kw)
+        return torch.full((N, D), 0.5)
+    eps_calls = []
+    orig_noised = ddpm.compute_noised_representation
+
+    def noised(xh, batch_index, node_mask, gamma_t, generate_x_only=False, eps=None):
+        eps_calls.append(eps)
+        return orig_noised(xh, batch_index, node_mask, gamma_t, generate_x_only=generate_x_only, eps=eps)
+    randn_calls = []
+    orig_randn = torch.randn
+
+    def randn(*a, **k):
+        randn_calls.append(tuple(a[0]))
+        return orig_randn(*a, **k)
+    monkeypatch.setattr(ddpm, "sample_p_zs_given_zt", fake_jump)
+    monkeypatch.setattr(ddpm, "compute_noised_representation", noised)
+    monkeypatch.setattr(torch, "randn", randn)
+    batch = pkg.config.AttrDict(x=inp["x"], h={"categorical": inp["one_hot"], "integer": inp["charges"]}, batch=bi, mask=mask, num_graphs=2,
+                                num_nodes_present=nn_, props_context=None)
+    noise = draws[:entries] if entries else None
+    out = ddpm(batch, t_int=inp["t_int"].long().view(-1, 1), noise=noise, self_conditioning_prob=1.0)
+    assert len(eps_calls) == 2 and len(net.calls) == 1
+    if entries == 3:
+        assert eps_calls[0] is draws[0] and eps_calls[1] is draws[1] and seen["noise"] is draws[2] and randn_calls == []
+    elif entries == 1:
+        assert eps_calls[0] is draws[0] and eps_calls[1] is None and seen["noise"] is None and randn_calls == [(N, 3), (N, D - 3)]          # z_sc; the jump is the stub's
+    else:
+        assert eps_calls == [None, None] and seen["noise"] is None and randn_calls == [(N, 3), (N, D - 3)] * 2
+    # the jump goes from t + 1 to 0 under no_grad, the estimate reaches the one evaluation that carries the tape
+    assert torch.equal(seen["t"], (inp["t_int"].long().view(-1, 1) + 1) / ddpm.T) and not seen["s"].any() and not seen["grad"] and seen["self_condition"]
+    assert net.calls[0]["grad"] and torch.equal(net.calls[0]["xh_self_cond"], torch.full((N, D), 0.5)) and not net.calls[0]["xh_self_cond"].requires_grad
+    assert out[1].requires_grad
+    # a T in t_int suppresses the branch whatever the probability
+    eps_calls.clear(), net.calls.clear()
+    ddpm(batch, t_int=torch.tensor([[7], [ddpm.T]]), noise=draws, self_conditioning_prob=1.0)
+    assert len(eps_calls) == 1 and net.calls[0]["xh_self_cond"] is None
+
+
+def test_training_step_forwards_self_conditioning_prob(monkeypatch):
+    model = pkg.QM9MoleculeGenerationDDPM(**pkg.default_cfgs("qm9")).train()
+    got = {}
+
+    def fake(batch, **kw):
+        got.update(kw)
+        z = torch.zeros(2, requires_grad=True)
+        return (z, z, z, z, z, z, z, z, torch.zeros(2), {})
+    monkeypatch.setattr(model.ddpm, "forward", fake)
+    b = pkg.config.AttrDict(x=torch.zeros(4, 3), one_hot=torch.zeros(4, 5), charges=torch.zeros(4), batch=torch.tensor([0, 0, 1, 1]), mask=torch.ones(4, dtype=torch.bool))
+    model.training_step(b, self_conditioning_prob=1.0)
+    assert got["self_conditioning_prob"] == 1.0
+    model.training_step(b)
+    assert got["self_conditioning_prob"] == 0.5
 
 
 def test_paths_and_reasons_without_a_gpu():
