@@ -10,6 +10,7 @@
 #include "../../include/gcdm_hip.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -81,8 +82,16 @@ struct gcdm_handle {
     int fuse_node = 1;               // option "fuse_node" / env GCDM_FUSE_NODE: 1 = the layer's node tiles run as a tail role of the persistent edge workgroups (one launch
                                      // per layer) where the plan qualifies; 0 = two launches per layer (rounds 1-5)
     int fuse_active = 0;             // option "fuse_active" (read-only): the last forward used the fused launch
-    uint32_t* d_flags = nullptr;
+    uint32_t* d_flags = nullptr;        // FlagBlock (gcdm_kernels.hip.h): plan-wide flag word, statistics of gcdm_encode_samples, the packed plan's tables for the NaN sites
     float* d_gmean = nullptr;
+    // packed plan (gcdm_plan_batches): K sub-batches end to end; K = 0: an ordinary plan, the tables are null and every kernel takes its usual path
+    int K = 0;
+    int *d_mol_sub = nullptr, *d_sub_noff = nullptr;
+    uint64_t* d_seeds = nullptr;
+    uint32_t* d_sub_flags = nullptr;
+    int* d_tvalid = nullptr;            // real edges of every 64-group of the (padded) edge list: a sub-batch's edges start on a 64-edge boundary
+    int64_t E_real = 0;                 // edges without that padding (E counts the slots of the list)
+    PackTab pack() const { return PackTab{d_mol_sub, d_sub_noff, d_seeds, d_sub_flags}; }
     int flat_prev = 0, flat_next = 0;   // the plan is a slice of a larger flat batch (options "flat_prev" / "flat_next"; include/gcdm_hip.h)
     uint32_t node_base = 0;             // option "node_base": flat index of the slice's first node (Philox counter)
     int fix_noise = 0;                  // option "fix_noise": x-noise centred over the whole flat batch (mol_gen_sample(fix_noise=True))
@@ -136,6 +145,11 @@ namespace {
 int fail(gcdm_handle* h, const std::string& msg) {
     if (h) h->err = msg;
     return -1;
+}
+
+// Entry points and options a packed plan does not serve (include/gcdm_hip.h): refused with a message, the handle and its plan stay as they are
+int refuse_packed(gcdm_handle* h, const char* what) {
+    return fail(h, std::string(what) + ": not available under a packed plan (gcdm_plan_batches); plan with gcdm_plan_batch first");
 }
 
 // Anything a captured step has baked in changed (plan, weights, gamma table, an option): drop the instantiated graph
@@ -496,6 +510,17 @@ void free_plan(gcdm_handle* h) {
     if (h->d_tail_ctr) (void)hipFree(h->d_tail_ctr);
     h->d_tail_ctr = nullptr;
     if (h->ws) (void)hipFree(h->ws);
+    if (h->K) {
+        if (h->d_flags) (void)hipMemset(reinterpret_cast<char*>(h->d_flags) + offsetof(FlagBlock, num_sub), 0, sizeof(FlagBlock) - offsetof(FlagBlock, num_sub));
+        if (h->d_mol_sub) (void)hipFree(h->d_mol_sub);
+        if (h->d_sub_noff) (void)hipFree(h->d_sub_noff);
+        if (h->d_seeds) (void)hipFree(h->d_seeds);
+        if (h->d_sub_flags) (void)hipFree(h->d_sub_flags);
+        if (h->d_tvalid) (void)hipFree(h->d_tvalid);
+        h->d_tvalid = nullptr;
+        h->d_mol_sub = h->d_sub_noff = nullptr; h->d_seeds = nullptr; h->d_sub_flags = nullptr;
+        h->K = 0;
+    }
     h->d_noff = h->d_erow = h->d_ecol = h->d_ncnt = h->d_rowstart = nullptr;
     h->ws = nullptr;
     h->B = h->N = 0;
@@ -550,8 +575,8 @@ int gcdm_create(const GcdmConfig* cfg, gcdm_handle** out) {
         int n = 0;
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && n > 0) h->cus = n;
     }
-    HIP_OK(h, hipMalloc(&h->d_flags, 4 * sizeof(uint32_t)));            // [0] flag word, [1..2] statistics of gcdm_encode_samples
-    HIP_OK(h, hipMemset(h->d_flags, 0, 4 * sizeof(uint32_t)));
+    HIP_OK(h, hipMalloc(&h->d_flags, sizeof(FlagBlock)));               // [0] flag word, [1..2] statistics of gcdm_encode_samples, then the packed plan's tables
+    HIP_OK(h, hipMemset(h->d_flags, 0, sizeof(FlagBlock)));
     return 0;
 }
 
@@ -843,6 +868,8 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
             set_lds_attr(h, k_edge_msg_x3<64, 16, 64>, EdgeGeo<64>::LDS_BYTES_X3) || set_lds_attr(h, k_edge_msg_x3<16, 8, 64>, EdgeGeo<64>::LDS_BYTES_X3) ||
             set_lds_attr(h, k_edge_msg_x3<64, 16, 32>, EdgeGeo<32>::LDS_BYTES_X3) || set_lds_attr(h, k_edge_msg_x3<16, 8, 32>, EdgeGeo<32>::LDS_BYTES_X3) ||
             set_lds_attr(h, k_edge_msg_x3<64, 16, 64, NodeTailRole<32>>, NodeTailRole<32>::LDS_BYTES) || set_lds_attr(h, k_edge_msg_x3<16, 8, 64, NodeTailRole<32>>, NodeTailRole<32>::LDS_BYTES) ||
+            set_lds_attr(h, k_edge_msg_x3<64, 16, 64, PackedRole>, EdgeGeo<64>::LDS_BYTES_X3) || set_lds_attr(h, k_edge_msg_x3<16, 8, 64, PackedRole>, EdgeGeo<64>::LDS_BYTES_X3) ||
+            set_lds_attr(h, k_edge_msg_x3<64, 16, 32, PackedRole>, EdgeGeo<32>::LDS_BYTES_X3) || set_lds_attr(h, k_edge_msg_x3<16, 8, 32, PackedRole>, EdgeGeo<32>::LDS_BYTES_X3) ||
             set_lds_attr(h, k_node_x3<true>, NK_LDS_BYTES) || set_lds_attr(h, k_node_x3<false>, NK_LDS_BYTES) || set_lds_attr(h, k_node_x3w, NW_LDS_BYTES) ||
             set_lds_attr(h, k_node<true>, NK_LDS_BYTES) || set_lds_attr(h, k_node<false>, NK_LDS_BYTES) ||
             set_lds_attr(h, k_node_x3<true, 4>, NK_LDS_BYTES) || set_lds_attr(h, k_node<true, 4>, NK_LDS_BYTES))
@@ -877,9 +904,41 @@ int gcdm_finalize_weights(gcdm_handle* h) {
     return 0;
 }
 
-int gcdm_plan_batch(gcdm_handle* h, int32_t B, const int32_t* nn) { return gcdm_plan_batch_masked(h, B, nn, nullptr); }
+static int plan_impl(gcdm_handle* h, int32_t B, const int32_t* nn, const uint8_t* node_mask, int32_t K, const int32_t* mols_per_batch);
+
+int gcdm_plan_batch(gcdm_handle* h, int32_t B, const int32_t* nn) { return plan_impl(h, B, nn, nullptr, 0, nullptr); }
 
 int gcdm_plan_batch_masked(gcdm_handle* h, int32_t B, const int32_t* nn, const uint8_t* node_mask) {
+    if (h && h->K && node_mask) return refuse_packed(h, "gcdm_plan_batch_masked");
+    return plan_impl(h, B, nn, node_mask, 0, nullptr);
+}
+
+int gcdm_plan_batches(gcdm_handle* h, int32_t K, const int32_t* mols_per_batch, const int32_t* nn) {
+    if (!h || K <= 0 || !mols_per_batch || !nn) return fail(h, "gcdm_plan_batches: bad argument");
+    if (h->sc) return fail(h, "gcdm_plan_batches: a self-conditioned model is not served by a packed plan");
+    if (h->fix_noise || h->flat_prev || h->flat_next || h->node_base)
+        return fail(h, "gcdm_plan_batches: the options fix_noise / flat_prev / flat_next / node_base must be 0 (a packed plan does not serve them)");
+    int64_t B = 0;
+    for (int k = 0; k < K; ++k) {
+        if (mols_per_batch[k] <= 0) return fail(h, "gcdm_plan_batches: every sub-batch needs >= 1 molecule");
+        B += mols_per_batch[k];
+    }
+    if (B >= (int64_t)1 << 31) return fail(h, "gcdm_plan_batches: too many molecules");
+    return plan_impl(h, (int32_t)B, nn, nullptr, K, mols_per_batch);
+}
+
+int gcdm_set_batch_seeds(gcdm_handle* h, int32_t K, const uint64_t* host_seeds) {
+    if (!h || !host_seeds) return fail(h, "gcdm_set_batch_seeds: bad argument");
+    if (!h->K) return fail(h, "gcdm_set_batch_seeds: the handle has no packed plan (gcdm_plan_batches)");
+    if (K != h->K) return fail(h, "gcdm_set_batch_seeds: num_batches differs from the packed plan's");
+    DeviceGuard guard(h->cfg.device);
+    // the table keeps its address (a captured step reads it), so nothing that may still read the old seeds is in flight when it changes
+    HIP_OK(h, hipDeviceSynchronize());
+    HIP_OK(h, hipMemcpy(h->d_seeds, host_seeds, (size_t)K * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+static int plan_impl(gcdm_handle* h, int32_t B, const int32_t* nn, const uint8_t* node_mask, int32_t K, const int32_t* mols_per_batch) {
     if (!h || B <= 0 || !nn) return fail(h, "gcdm_plan_batch: bad argument");
     DeviceGuard guard(h->cfg.device);
     drop_step_graph(h);
@@ -887,8 +946,14 @@ int gcdm_plan_batch_masked(gcdm_handle* h, int32_t B, const int32_t* nn, const u
     int64_t E = 0;
     int max_n = 0;
     bool masked = false;
+    // packed plan: first molecule of every sub-batch.  The edges of a sub-batch start on a 64-edge boundary of the flat edge list (the slots up to it repeat the last
+    // edge in front of them and are no part of any row: EdgeMsgArgs::TVALID) -- tile boundaries then cut its rows exactly where they cut them in a plan of its own, which
+    // is what makes its partial row sums (AggSrc), and so its results, those of the single run bit for bit.  64 covers both tile sizes.
+    std::vector<char> sub_first(B, 0);
+    for (int k = 0, b = 0; k < K; b += mols_per_batch[k], ++k) sub_first[b] = 1;
     for (int b = 0; b < B; ++b) {
         if (nn[b] <= 0) return fail(h, "gcdm_plan_batch: every molecule needs >= 1 atom");
+        if (sub_first[b]) E = (E + 63) / 64 * 64;
         noff[b + 1] = noff[b] + nn[b];
         int64_t m = nn[b];
         if (node_mask) {            // edges only between unmasked atoms of a molecule (get_fully_connected_edge_index, gcpnet.py:1062-1065)
@@ -910,8 +975,14 @@ int gcdm_plan_batch_masked(gcdm_handle* h, int32_t B, const int32_t* nn, const u
     const int N = noff[B];
     std::vector<int> erow(E), ecol(E), ncnt(N), rowstart(N);
     int64_t p = 0;
+    std::vector<int> tvalid;
+    if (K > 0) tvalid.assign((size_t)((E + 63) / 64), 64);
     for (int b = 0; b < B; ++b) {
         const int o = noff[b], n = nn[b];
+        if (sub_first[b] && (p & 63)) {
+            tvalid[(size_t)(p >> 6)] = (int)(p & 63);
+            for (; p & 63; ++p) { erow[p] = erow[p - 1]; ecol[p] = ecol[p - 1]; }
+        }
         int m = n;
         if (node_mask) { m = 0; for (int i = 0; i < n; ++i) m += node_mask[o + i] ? 1 : 0; }
         for (int i = 0; i < n; ++i) {
@@ -923,6 +994,7 @@ int gcdm_plan_batch_masked(gcdm_handle* h, int32_t B, const int32_t* nn, const u
                 if (!node_mask || node_mask[o + j]) { erow[p] = o + i; ecol[p] = o + j; ++p; }
         }
     }
+    if (K > 0 && (p & 63)) tvalid[(size_t)(p >> 6)] = (int)(p & 63);
     if (node_mask) {
         std::vector<float> mf(N);
         for (int i = 0; i < N; ++i) mf[i] = node_mask[i] ? 1.f : 0.f;
@@ -962,12 +1034,40 @@ int gcdm_plan_batch_masked(gcdm_handle* h, int32_t B, const int32_t* nn, const u
     h->PQ4b = w + oPQb; h->VDIb = w + oVDIb; h->VDJb = w + oVDJb;
     h->X0SC = h->sc ? w + oX0SC : nullptr; h->BL = h->sc ? w + oBL : nullptr; h->USC = h->sc ? w + oUSC : nullptr;
     h->B = B; h->N = N; h->E = E; h->max_n = max_n;
+    h->E_real = 0;
+    for (int i = 0; i < N; ++i) h->E_real += ncnt[i];
+    if (K > 0) {            // packed plan: the same topology, plus the sub-batch of each molecule, the first node of each sub-batch, the seeds and the flag words
+      auto tables = [&]() -> int {
+        std::vector<int> mol_sub(B), sub_noff(K + 1, 0);
+        for (int k = 0, b = 0; k < K; ++k) {
+            for (int j = 0; j < mols_per_batch[k]; ++j, ++b) mol_sub[b] = k;
+            sub_noff[k + 1] = noff[b];
+        }
+        h->K = K;           // (from here on free_plan releases the tables)
+        HIP_OK(h, hipMalloc(&h->d_mol_sub, (size_t)B * sizeof(int)));
+        HIP_OK(h, hipMalloc(&h->d_sub_noff, (size_t)(K + 1) * sizeof(int)));
+        HIP_OK(h, hipMalloc(&h->d_seeds, (size_t)K * sizeof(uint64_t)));
+        HIP_OK(h, hipMalloc(&h->d_sub_flags, (size_t)K * sizeof(uint32_t)));
+        HIP_OK(h, hipMalloc(&h->d_tvalid, tvalid.size() * sizeof(int)));
+        HIP_OK(h, hipMemcpy(h->d_tvalid, tvalid.data(), tvalid.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIP_OK(h, hipMemcpy(h->d_mol_sub, mol_sub.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+        HIP_OK(h, hipMemcpy(h->d_sub_noff, sub_noff.data(), (size_t)(K + 1) * sizeof(int), hipMemcpyHostToDevice));
+        HIP_OK(h, hipMemset(h->d_seeds, 0, (size_t)K * sizeof(uint64_t)));
+        HIP_OK(h, hipMemset(h->d_sub_flags, 0, (size_t)K * sizeof(uint32_t)));
+        FlagBlock fb{};
+        fb.num_sub = (uint32_t)K; fb.sub_noff = h->d_sub_noff; fb.sub_flags = h->d_sub_flags;
+        HIP_OK(h, hipMemcpy(reinterpret_cast<char*>(h->d_flags) + offsetof(FlagBlock, num_sub), reinterpret_cast<const char*>(&fb) + offsetof(FlagBlock, num_sub),
+                            sizeof(FlagBlock) - offsetof(FlagBlock, num_sub), hipMemcpyHostToDevice));
+        return 0;
+      };
+      if (tables()) { free_plan(h); return -1; }          // (no plan rather than one with half its tables)
+    }
     // ---- node-tile queues of the fused layer launch (gcdm_layer_x3.hip.h): 64-edge tiles, XCD x owns the x-th contiguous eighth of the tile list (the partition of
     // k_edge_msg_x3's persistent loop); node tile t (T nodes) waits for the edge tiles first_tile(t) .. last_tile(t) of its rows and is owned by the XCD whose range
     // contains first_tile(t).  A plan qualifies when nothing is masked, the launch is persistent and no node tile spans three XCDs.
     h->tail_tiles32 = 0;
     const int wgs_ = h->cus / 8 * 8;
-    if (!node_mask && E > (int64_t)64 * wgs_ && wgs_ >= 8) {
+    if (!node_mask && K == 0 && E > (int64_t)64 * wgs_ && wgs_ >= 8) {          // (a packed plan runs two launches per layer: its padded edge list is not what the queues below describe)
         const int G = (int)((E + 63) / 64), base = G >> 3, rem = G & 7;
         int xs[9];
         for (int x = 0; x <= 8; ++x) xs[x] = x * base + std::min(x, rem);
@@ -1026,7 +1126,7 @@ int gcdm_bond_orders(const GcdmBondTables* tables, const float* x, int64_t x_row
 }
 
 int64_t gcdm_num_nodes(const gcdm_handle* h) { return h ? h->N : -1; }
-int64_t gcdm_num_edges(const gcdm_handle* h) { return h ? h->E : -1; }
+int64_t gcdm_num_edges(const gcdm_handle* h) { return h ? h->E_real : -1; }
 
 int gcdm_debug_set_layer_limit(gcdm_handle* h, int32_t n) {
     if (!h) return -1;
@@ -1046,19 +1146,22 @@ static int node_tile_for(const gcdm_handle* h, int N) {
     return 1.55f * r64 < (float)r32 ? 64 : 32;
 }
 
-int gcdm_forward(gcdm_handle* h, const float* xh, const float* t, const float* context, float* out, uint32_t* flags, void* stream_) {
-    return gcdm_forward_sc(h, xh, nullptr, t, context, out, flags, stream_);
-}
-
 // The sampler's network evaluations (transition, gcdm_sample_final_sc) feed the time from the step instead of a t [N] tensor and fold the last stage
 // (k_finish) into their k_sample launch: one value for the whole batch, from the device step table when the step is being captured
 struct StepFeed { const StepRow* rows; int* cursor; float t_value; };
 static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, const float* t, const StepFeed* feed, const float* context, float* out,
                         uint32_t* flags, void* stream_);
 
+int gcdm_forward(gcdm_handle* h, const float* xh, const float* t, const float* context, float* out, uint32_t* flags, void* stream_) {
+    if (!h) return -1;
+    if (!t) return fail(h, "gcdm_forward: null tensor");
+    return forward_impl(h, xh, nullptr, t, nullptr, context, out, flags, stream_);
+}
+
 int gcdm_forward_sc(gcdm_handle* h, const float* xh, const float* xh_sc, const float* t, const float* context, float* out, uint32_t* flags,
                     void* stream_) {
     if (!h) return -1;
+    if (h->K) return refuse_packed(h, "gcdm_forward_sc");
     if (!t) return fail(h, "gcdm_forward: null tensor");
     return forward_impl(h, xh, xh_sc, t, nullptr, context, out, flags, stream_);
 }
@@ -1080,6 +1183,7 @@ static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, con
                 h->sc, xh_sc, h->X0SC, h->d_mask};
     if (feed) { pa.t = nullptr; pa.t_rows = feed->rows; pa.t_cursor = feed->cursor; pa.t_value = feed->t_value; }
     pa.flags_dev = h->d_flags;            // cleared by the first kernel of the evaluation
+    pa.pack = h->pack();
     hipLaunchKernelGGL(k_prep, dim3(B), dim3(64), 3 * h->max_n * sizeof(float), st, pa);
     EdgeEmbedArgs ea{h->X0, h->XC, N, h->d_erow, h->d_ecol, E, h->ee_ws, h->ee_bs, h->ee_wd, h->ee_wdf, h->ee_kappa, h->ee_wg, h->ee_bg,
                      (v4f*)h->EP4, h->AL, h->U, h->FR,
@@ -1160,6 +1264,7 @@ static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, con
         for (int k = 0; k < 3; ++k) ma.mk[k] = d.mk[k];
         ma.wa = d.wa; ma.ba = d.ba;
         ma.prof = h->profile_phases ? h->PROF : nullptr;
+        ma.TVALID = h->d_tvalid;
         if (h->profile) HIP_OK(h, hipEventRecord(h->ev[2 * l], st));
         if (h->use_x3()) {
             EdgeMsgX3Args xa{};
@@ -1204,6 +1309,16 @@ static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, con
                 }
                 continue;
             }
+            if (h->K) {             // packed plan: the same kernel with the tiles' real edge counts
+                PackedRole::Args lp{xa};
+                if (ET == 64) {
+                    if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 64, PackedRole>), dim3(wgs), dim3(512), EdgeGeo<64>::LDS_BYTES_X3, st, lp);
+                    else hipLaunchKernelGGL((k_edge_msg_x3<16, 8, 64, PackedRole>), dim3(wgs), dim3(512), EdgeGeo<64>::LDS_BYTES_X3, st, lp);
+                } else {
+                    if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 32, PackedRole>), dim3(wgs), dim3(256), EdgeGeo<32>::LDS_BYTES_X3, st, lp);
+                    else hipLaunchKernelGGL((k_edge_msg_x3<16, 8, 32, PackedRole>), dim3(wgs), dim3(256), EdgeGeo<32>::LDS_BYTES_X3, st, lp);
+                }
+            } else {
             NoTailRole::Args la{xa};
             if (ET == 64) {
                 if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 64>), dim3(wgs), dim3(512), EdgeGeo<64>::LDS_BYTES_X3, st, la);
@@ -1211,6 +1326,7 @@ static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, con
             } else {
                 if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 32>), dim3(wgs), dim3(256), EdgeGeo<32>::LDS_BYTES_X3, st, la);
                 else hipLaunchKernelGGL((k_edge_msg_x3<16, 8, 32>), dim3(wgs), dim3(256), EdgeGeo<32>::LDS_BYTES_X3, st, la);
+            }
             }
         } else if (ET == 64) {
             if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg<64, 16, 64>), dim3(tiles), dim3(EdgeGeo<64>::THREADS), EdgeGeo<64>::LDS_BYTES, st, ma);
@@ -1226,7 +1342,7 @@ static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, con
         if (h->profile) HIP_OK(h, hipEventRecord(h->ev[2 * (size_t)h->L + l], st));      // end of the layer's node kernel (gcdm_profile_node_kernel_ms)
     }
     if (!truncated && !feed) {              // (the sampler's evaluations: inside their k_sample launch)
-        FinishArgs fa{h->VEL, h->d_noff, N, h->D, out, h->d_flags, flags, h->d_mask};
+        FinishArgs fa{h->VEL, h->d_noff, N, h->D, out, h->d_flags, flags, h->d_mask, h->pack()};
         hipLaunchKernelGGL(k_finish, dim3(B), dim3(64), 0, st, fa);
     }
     HIP_OK(h, hipGetLastError());
@@ -1253,6 +1369,7 @@ static int launch_sample(gcdm_handle* h, StepArgs& sa, hipStream_t st) {
     if (h->d_mask) return fail(h, "the sampler entry points need an all-True node mask (plan with gcdm_plan_batch); masked plans serve gcdm_forward only");
     DeviceGuard guard(h->cfg.device);
     sa.noff = h->d_noff; sa.N = h->N; sa.D = h->D; sa.node_base = h->node_base;
+    sa.pack = h->pack();
     if (h->fix_noise) {                 // pre-pass: mean of this draw over all nodes (deterministic order)
         if (!h->d_gmean) HIP_OK(h, hipMalloc(&h->d_gmean, 4 * sizeof(float)));
         hipLaunchKernelGGL(k_noise_mean, dim3(1), dim3(1024), 0, st, sa.noise, sa.seed, sa.draw, h->node_base, h->N, h->D, h->d_gmean);
@@ -1272,6 +1389,7 @@ int gcdm_sample_init(gcdm_handle* h, float* z, const float* noise, uint64_t seed
 
 int gcdm_encode_samples(gcdm_handle* h, const float* xh, float* z, uint32_t* flags, void* stream_) {
     if (!h || !xh || !z || !h->N) return fail(h, "gcdm_encode_samples: bad argument / no plan");
+    if (h->K) return refuse_packed(h, "gcdm_encode_samples");
     DeviceGuard guard(h->cfg.device);
     hipStream_t st = (hipStream_t)stream_;
     HIP_OK(h, hipMemsetAsync(h->d_flags + 1, 0, 2 * sizeof(uint32_t), st));
@@ -1398,6 +1516,7 @@ int gcdm_sample_step_to(gcdm_handle* h, const float* z_in, float* z_out, const f
     if (!h || !z_in || !z_out || num_steps <= 0 || s_index < 0 || s_index >= num_steps) return fail(h, "gcdm_sample_step: bad argument");
     if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_sample_step: gamma table not set");
     // s = s_index / num_steps, t = (s_index + 1) / num_steps (variational_diffusion.py:1335-1341); t [N] = t[batch_index] (:1239)
+    if (h->K) seed = 0;                // packed plan: the seeds are the table's (gcdm_set_batch_seeds); one value here, so that the captured step is not re-captured per caller seed
     if (z_in == z_out && !noise) {
         const int g = step_via_graph(h, z_out, context, s_index, num_steps, seed, flags, (hipStream_t)stream_);
         if (g != 0) return g < 0 ? -1 : 0;
@@ -1409,6 +1528,7 @@ int gcdm_sample_step_to(gcdm_handle* h, const float* z_in, float* z_out, const f
 int gcdm_sample_step_sc(gcdm_handle* h, float* z, float* self_cond, int32_t have_self_cond, const float* context, int32_t s_index,
                         int32_t num_steps, const float* noise, const float* noise_self_cond, uint64_t seed, uint32_t* flags, void* stream_) {
     if (!h || !z || !self_cond || num_steps <= 0 || s_index < 0 || s_index >= num_steps) return fail(h, "gcdm_sample_step_sc: bad argument");
+    if (h->K) return refuse_packed(h, "gcdm_sample_step_sc");
     if (!h->sc) return fail(h, "gcdm_sample_step_sc: the handle was created without self_condition");
     if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_sample_step_sc: gamma table not set");
     const float s = (float)s_index / (float)num_steps, t = (float)(s_index + 1) / (float)num_steps;
@@ -1418,13 +1538,22 @@ int gcdm_sample_step_sc(gcdm_handle* h, float* z, float* self_cond, int32_t have
     return transition(h, z, self_cond, nullptr, context, 0.0f, s, noise_self_cond, seed, 0x20000000u | (uint32_t)s_index, flags, stream_);
 }
 
+static int sample_final_impl(gcdm_handle* h, const float* z0, const float* self_cond, const float* context, const float* noise, uint64_t seed,
+                             float* out, uint32_t* flags, void* stream_);
+
 int gcdm_sample_final(gcdm_handle* h, const float* z0, const float* context, const float* noise, uint64_t seed, float* out, uint32_t* flags,
                       void* stream_) {
-    return gcdm_sample_final_sc(h, z0, nullptr, context, noise, seed, out, flags, stream_);
+    return sample_final_impl(h, z0, nullptr, context, noise, seed, out, flags, stream_);
 }
 
 int gcdm_sample_final_sc(gcdm_handle* h, const float* z0, const float* self_cond, const float* context, const float* noise, uint64_t seed,
                          float* out, uint32_t* flags, void* stream_) {
+    if (h && h->K) return refuse_packed(h, "gcdm_sample_final_sc");
+    return sample_final_impl(h, z0, self_cond, context, noise, seed, out, flags, stream_);
+}
+
+static int sample_final_impl(gcdm_handle* h, const float* z0, const float* self_cond, const float* context, const float* noise, uint64_t seed,
+                             float* out, uint32_t* flags, void* stream_) {
     if (!h || !z0 || !out) return fail(h, "gcdm_sample_final: bad argument");
     if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_sample_final: gamma table not set");
     DeviceGuard guard(h->cfg.device);
@@ -1444,7 +1573,7 @@ int gcdm_sample_final_sc(gcdm_handle* h, const float* z0, const float* self_cond
     sa.user_flags = flags; sa.flags_dev = h->d_flags;
     if (launch_sample(h, sa, st)) return -1;
     // CoG drift re-projection is a whole-batch decision in the reference (:1389-1402); only "for examples without intermediate states"
-    if (h->cog_fix) hipLaunchKernelGGL(k_cog_fix, dim3(h->B), dim3(64), 0, st, out, h->d_noff, h->D, h->d_flags, flags);
+    if (h->cog_fix) hipLaunchKernelGGL(k_cog_fix, dim3(h->B), dim3(64), 0, st, out, h->d_noff, h->D, h->d_flags, flags, h->pack());
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -1452,6 +1581,7 @@ int gcdm_sample_final_sc(gcdm_handle* h, const float* z0, const float* self_cond
 // ---- RePaint inpainting (variational_diffusion.py:1582-1789) ----
 int gcdm_inpaint_center(gcdm_handle* h, const float* xh, const uint8_t* fixed, float* xh0, void* stream_) {
     if (!h || !xh || !fixed || !xh0 || !h->N) return fail(h, "gcdm_inpaint_center: bad argument / no plan");
+    if (h->K) return refuse_packed(h, "gcdm_inpaint_center");
     DeviceGuard guard(h->cfg.device);
     hipLaunchKernelGGL(k_inpaint_center, dim3(h->B), dim3(64), 0, (hipStream_t)stream_, xh, fixed, h->d_noff, h->D, xh0);
     HIP_OK(h, hipGetLastError());
@@ -1462,6 +1592,7 @@ int gcdm_inpaint_step(gcdm_handle* h, float* z, const float* xh0, const uint8_t*
                       const float* context, int32_t s_index, int32_t num_steps, const float* noise_known, const float* noise_unknown,
                       const float* noise_self_cond, uint64_t seed, uint32_t draw_base, uint32_t* flags, void* stream_) {
     if (!h || !z || !xh0 || !fixed || num_steps <= 0 || s_index < 0 || s_index >= num_steps || !h->N) return fail(h, "gcdm_inpaint_step: bad argument / no plan");
+    if (h->K) return refuse_packed(h, "gcdm_inpaint_step");
     if ((h->sc != 0) != (self_cond != nullptr)) return fail(h, "gcdm_inpaint_step: self_cond must be given exactly when the handle has self_condition");
     if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_inpaint_step: gamma table not set");
     DeviceGuard guard(h->cfg.device);
@@ -1485,6 +1616,7 @@ int gcdm_inpaint_step(gcdm_handle* h, float* z, const float* xh0, const uint8_t*
 int gcdm_inpaint_jump(gcdm_handle* h, float* z, int32_t s_index, int32_t t_index, int32_t num_steps, const float* noise, uint64_t seed,
                       uint32_t draw, void* stream_) {
     if (!h || !z || num_steps <= 0 || s_index < 0 || t_index <= s_index || t_index > num_steps || !h->N) return fail(h, "gcdm_inpaint_jump: bad argument / no plan");
+    if (h->K) return refuse_packed(h, "gcdm_inpaint_jump");
     if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_inpaint_jump: gamma table not set");
     // q(z_t | z_s) (sample_p_zt_given_zs, :1163-1201; sigma_and_alpha_t_given_s :342-367)
     const float gs = gamma_lookup(h, (float)s_index / (float)num_steps), gt = gamma_lookup(h, (float)t_index / (float)num_steps);
@@ -1515,6 +1647,7 @@ int gcdm_set_option(gcdm_handle* h, const char* name, int32_t value) {
     if (k == "cog_fix") { h->cog_fix = value ? 1 : 0; return 0; }
     // (the getters of the options below return the stored field itself -- edge_tile: the effective tile, which is what a captured step bakes in; an option whose
     //  getter normalises its value must be added to the always-drop list beside mfma_mode)
+    if (h->K && value != 0 && (k == "fix_noise" || k == "flat_prev" || k == "flat_next" || k == "node_base")) return refuse_packed(h, ("gcdm_set_option(" + k + ")").c_str());
     if (gcdm_get_option(h, name) != value || k == "mfma_mode" || k == "fuse_node") drop_step_graph(h);
     if (k == "mfma_mode") {                 // 0: fp32 MFMA, 1: split-precision f16 x3 (fp32-equivalent, 5.3x the matrix rate)
         if (value != 0 && value != 1) return fail(h, "gcdm_set_option(mfma_mode): 0 or 1");
@@ -1558,6 +1691,7 @@ int gcdm_get_option(const gcdm_handle* h, const char* name) {
     if (k == "node_tile") return h->node_tile;
     if (k == "step_graph") return (h->step_graph && !h->step_graph_failed) ? 1 : 0;
     if (k == "graph_launches") return (int)(h->graph_launches & 0x7fffffff);
+    if (k == "num_batches") return h->K;
     return -1;
 }
 

@@ -1024,6 +1024,15 @@ struct EdgeMsgX3Args {
 // +11 % cycles per edge tile, more than the balance returns.
 struct NoTailRole {
     static constexpr bool ON = false;
+    static constexpr bool PACKED = false;
+    struct Args { EdgeMsgX3Args e; };
+};
+// The kernel by itself on the edge list of a packed plan (gcdm_plan_batches): every sub-batch starts on a 64-edge boundary, so that tile boundaries cut its rows where
+// they cut them in a plan of its own -- the partial sums of a cut row (AggSrc) and with them every bit of the result depend on that.  The slots between a sub-batch's
+// last edge and the boundary repeat that edge (every load stays an ordinary one) and are kept out of the row segments: EdgeMsgArgs::TVALID gives the tile's real edges.
+struct PackedRole {
+    static constexpr bool ON = false;
+    static constexpr bool PACKED = true;
     struct Args { EdgeMsgX3Args e; };
 };
 
@@ -1220,7 +1229,8 @@ __global__ __launch_bounds__(ET * 8) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const uint32_t o0H = wp.off(ax.w0H + (size_t)mt0 * KB0C * 64), o0L = wp.off(ax.w0L + (size_t)mt0 * KB0C * 64);
     const int prof_tile = start_ + it_;
     const int e0 = prof_tile * ET;
-    const int nvalid = min(ET, E - e0);
+    int nvalid = min(ET, E - e0);
+    if constexpr (TR::PACKED) nvalid = min(nvalid, tile_valid<ET>(a.TVALID, e0));
     const int eid = min(e0 + e, E - 1);
     const int ni = ix.ni;
     [[maybe_unused]] const uint64_t t_start = a.prof ? __builtin_amdgcn_s_memtime() : 0;

@@ -365,6 +365,39 @@ __device__ __forceinline__ void frame_of(float xi0, float xi1, float xi2, float 
 // ================================================================================================
 // Step-dependent scalars of one ancestral transition, one row per step index, resident on the device: the kernels of a CAPTURED step (hipGraph,
 // gcdm_api.hip: StepGraph) read row [*cursor] instead of taking the values as launch arguments, so one instantiated graph serves every step.
+// Packed plan (gcdm_plan_batches, include/gcdm_hip.h): K independent flat batches ("sub-batches") laid end to end in ONE plan.  Each keeps what a flat batch
+// of its own has -- orientations zero padded at its two ends, its own Philox stream (counter = node index within the sub-batch, its own seed), its own NaN-in-vel
+// decision and CoG re-projection, its own word of the caller's flags.  The tables live in device memory at addresses that hold as long as the plan (a captured
+// step reads them); mol_sub == null <=> the plan is not packed and every kernel takes the path it always took.
+struct PackTab {
+    const int* mol_sub;          // [B]     sub-batch of each molecule
+    const int* sub_noff;         // [K + 1] first node of each sub-batch
+    const uint64_t* seeds;       // [K]     Philox seed of each sub-batch (gcdm_set_batch_seeds)
+    uint32_t* sub_flags;         // [K]     per-sub-batch flag words: bit 0 NaN in vel, bit 2 CoG drift (the range / tail bits stay in the handle's plan-wide word)
+};
+// first molecule of its sub-batch: the one workgroup that clears / reports the sub-batch's word
+__device__ __forceinline__ bool pack_first(const PackTab& p, const int* noff, int b, int& k) { k = p.mol_sub[b]; return noff[b] == p.sub_noff[k]; }
+
+// The handle's flag words as the device sees them (gcdm_handle::d_flags).  The layer node kernels raise "NaN in vel" through raise_nan_vel: under a packed plan
+// in the word of the node's sub-batch, found from the two table pointers kept HERE rather than in their launch arguments -- the site is reached only when a NaN
+// turns up, so the hot kernels carry no further argument.
+struct FlagBlock {
+    uint32_t word;               // plan-wide flag word, cleared by k_prep
+    uint32_t stat[2];            // statistics of gcdm_encode_samples
+    uint32_t num_sub;            // K of a packed plan, 0 otherwise
+    const int* sub_noff;         // PackTab::sub_noff
+    uint32_t* sub_flags;         // PackTab::sub_flags
+};
+__device__ __forceinline__ void raise_nan_vel(uint32_t* flags_dev, int node) {
+    const FlagBlock* fb = reinterpret_cast<const FlagBlock*>(flags_dev);
+    const int K = (int)fb->num_sub;
+    if (K == 0) { atomicOr(flags_dev, 1u); return; }
+    const int* so = fb->sub_noff;
+    int k = 0;
+    while (k + 1 < K && so[k + 1] <= node) ++k;
+    atomicOr(fb->sub_flags + k, 1u);
+}
+
 struct StepRow {
     float t;                            // network time of the step (k_prep puts it into the time column of h_in)
     float alpha_coef, c_eps, sigma;     // as in StepArgs
@@ -394,12 +427,20 @@ struct PrepArgs {
     // flags_dev: the handle's flag word, cleared here for the kernels behind (what a memset node did before round 6)
     const StepRow* t_rows; int* t_cursor; float t_value;       // t_cursor: the two slots of the step cursor (k_cursor_set)
     uint32_t* flags_dev;
+    PackTab pack;      // packed plan: a node's flat neighbours end at its sub-batch (mol_sub null: at the plan's ends, or beyond them with has_prev / has_next)
 };
 
 __global__ __launch_bounds__(64) void k_prep(PrepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float xs[];  // [3][n] centralised
     const int b = blockIdx.x, o = a.noff[b], n = a.noff[b + 1] - o, D = 3 + a.F;
     if (a.flags_dev && b == 0 && threadIdx.x == 0) *a.flags_dev = 0u;
+    int g_lo = 0, g_hi = a.N;                // flat range inside which a node has neighbours
+    if (a.pack.mol_sub) {
+        int k;
+        const bool first = pack_first(a.pack, a.noff, b, k);
+        g_lo = a.pack.sub_noff[k]; g_hi = a.pack.sub_noff[k + 1];
+        if (first && threadIdx.x == 0) a.pack.sub_flags[k] = 0u;
+    }
     float t_all = a.t_value;
     if (a.t_rows) {
         const int cur = a.t_cursor[0];
@@ -431,13 +472,13 @@ __global__ __launch_bounds__(64) void k_prep(PrepArgs a) {
         xs[i] = c0; xs[n + i] = c1; xs[2 * n + i] = c2;
         // orientations (protein_graph_dataset.py:217-225): flat neighbours, zero padded at the global ends
         float fw[3] = {0.f, 0.f, 0.f}, bw[3] = {0.f, 0.f, 0.f};
-        if (g + 1 < a.N || a.has_next) {
+        if (g + 1 < g_hi || a.has_next) {
             const float* q = p + D;
             const float mq = (a.mask && g + 1 < a.N) ? a.mask[g + 1] : 1.f;
             const float e0 = q[0] * mq - x0, e1 = q[1] * mq - x1, e2 = q[2] * mq - x2, nr = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
             if (nr > 0.f) { fw[0] = e0 / nr; fw[1] = e1 / nr; fw[2] = e2 / nr; }
         }
-        if (g > 0 || a.has_prev) {
+        if (g > g_lo || a.has_prev) {
             const float* q = p - D;
             const float mq = (a.mask && g > 0) ? a.mask[g - 1] : 1.f;
             const float e0 = q[0] * mq - x0, e1 = q[1] * mq - x1, e2 = q[2] * mq - x2, nr = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
@@ -451,12 +492,12 @@ __global__ __launch_bounds__(64) void k_prep(PrepArgs a) {
             const float s0 = ps ? ps[0] : 0.f, s1 = ps ? ps[1] : 0.f, s2 = ps ? ps[2] : 0.f;
             a.X0SC[g] = s0; a.X0SC[a.N + g] = s1; a.X0SC[2 * a.N + g] = s2;
             float fs[3] = {0.f, 0.f, 0.f}, bs_[3] = {0.f, 0.f, 0.f};
-            if (ps && (g + 1 < a.N || a.has_next)) {
+            if (ps && (g + 1 < g_hi || a.has_next)) {
                 const float* q = ps + D;
                 const float e0 = q[0] - s0, e1 = q[1] - s1, e2 = q[2] - s2, nr = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
                 if (nr > 0.f) { fs[0] = e0 / nr; fs[1] = e1 / nr; fs[2] = e2 / nr; }
             }
-            if (ps && (g > 0 || a.has_prev)) {
+            if (ps && (g > g_lo || a.has_prev)) {
                 const float* q = ps - D;
                 const float e0 = q[0] - s0, e1 = q[1] - s1, e2 = q[2] - s2, nr = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
                 if (nr > 0.f) { bs_[0] = e0 / nr; bs_[1] = e1 / nr; bs_[2] = e2 / nr; }
@@ -616,7 +657,16 @@ struct EdgeMsgArgs {
     GcpW mk[3];
     const float* wa; float ba;   // scalar_message_attention
     float* prof;                 // optional [tiles][8 waves][24] phase time stamps (shader cycles since kernel start)
+    // packed plan (gcdm_plan_batches), else null: real edges of every group of 64 flat edges.  A sub-batch's edges start on a 64-edge boundary -- where the tile
+    // boundaries cut its rows in a plan of its own -- and the slots behind its last edge up to the boundary repeat that edge; they belong to no row segment
+    const int* TVALID;
 };
+// real edges of the tile that starts at flat edge e0 (ET = 32: the tile is one half of a 64-group)
+template <int ET>
+__device__ __forceinline__ int tile_valid(const int* tvalid, int e0) {
+    const int v = tvalid[e0 >> 6];
+    return ET == 64 ? v : max(0, min(ET, v - (e0 & 63)));
+}
 
 // In-kernel phase time stamps are compiled in only with -DGCDM_STAMPS (tools/build_variants.sh; gcdm_profile_enable(h, 2 | 3) fails
 // without it): even switched off at run time each stamp costs the wave an exec-mask save, a branch and a restore -- 20 of them are
@@ -687,7 +737,8 @@ __global__ __launch_bounds__(EdgeGeo<ET>::THREADS) void k_edge_msg(EdgeMsgArgs a
     const int part = (ET == 64) ? wave : (tid / ET);
     const int E = a.E, N = a.N;
     const int e0 = blockIdx.x * ET;
-    const int nvalid = min(ET, E - e0);
+    int nvalid = min(ET, E - e0);
+    if (a.TVALID) nvalid = min(nvalid, tile_valid<ET>(a.TVALID, e0));
     const int eid = min(e0 + e, E - 1);
     const int ni = a.EROW[eid], nj = a.ECOL[eid];
     [[maybe_unused]] const int prof_tile = blockIdx.x;
@@ -1133,7 +1184,7 @@ __global__ __launch_bounds__(256) void k_node(NodeArgs a) {
         if (part < 3 && valid) {
             const float v = XP[part * NTP + e] - a.X0[(size_t)part * N + nid];
             a.VEL[(size_t)part * N + nid] = v;
-            if (v != v) atomicOr(a.flags_dev, 1u);
+            if (v != v) raise_nan_vel(a.flags_dev, nid);
         }
     }
 }
@@ -1144,13 +1195,19 @@ __global__ __launch_bounds__(256) void k_node(NodeArgs a) {
 struct FinishArgs {
     const float* VEL; const int* noff; int N, Dout; float* OUT; const uint32_t* flags_dev; uint32_t* user_flags;
     const float* mask;      // masked nodes (or null): vel is zero there and they are left out of the centroid (components/__init__.py:53-92)
+    PackTab pack;           // packed plan: the NaN decision and the caller's word are the sub-batch's (user_flags: K words), the range / tail bits go to every word
 };
 
 __global__ __launch_bounds__(64) void k_finish(FinishArgs a) {
     const int b = blockIdx.x, o = a.noff[b], n = a.noff[b + 1] - o;
-    const uint32_t fl = *a.flags_dev;
+    uint32_t fl = *a.flags_dev;
+    if (a.pack.mol_sub) {
+        int k;
+        const bool first = pack_first(a.pack, a.noff, b, k);
+        fl |= a.pack.sub_flags[k];
+        if (fl && a.user_flags && first && threadIdx.x == 0) atomicOr(a.user_flags + k, fl);
+    } else if (fl && a.user_flags && b == 0 && threadIdx.x == 0) atomicOr(a.user_flags, fl);   // NaN-vel / f16-range bits
     const bool nan = (fl & 1u) != 0;
-    if (fl && a.user_flags && b == 0 && threadIdx.x == 0) atomicOr(a.user_flags, fl);   // NaN-vel / f16-range bits
     float m0 = 0.f, m1 = 0.f, m2 = 0.f;
     if (!nan) {
         float cnt = 0.f;
@@ -1214,6 +1271,9 @@ struct StepArgs {
     // final decode
     float* out; int num_atom_types, include_charges; float nv0, nv1, nv2, nb1, nb2;
     uint32_t* user_flags; uint32_t* flags_dev;
+    // packed plan: seed = pack.seeds[sub-batch] (the `seed` above is ignored), Philox counter = node index within the sub-batch, NaN-in-vel / CoG drift decided and
+    // reported per sub-batch (user_flags: K words)
+    PackTab pack;
 };
 
 // the step cursor of a captured step, two slots: k_prep reads slot 0 and copies it to slot 1, k_sample reads slot 1 and writes slot 0 = slot 1 - 1
@@ -1221,10 +1281,18 @@ struct StepArgs {
 __global__ void k_cursor_set(int* cursor, int v) { cursor[0] = v; cursor[1] = v; }
 
 // whole-batch CoG re-projection if any molecule drifted (variational_diffusion.py:1389-1402)
-__global__ __launch_bounds__(64) void k_cog_fix(float* out, const int* noff, int D, const uint32_t* flags_dev, uint32_t* user_flags) {
-    if (!(*flags_dev & 4u)) return;
+// (packed plan: the decision of the molecule's sub-batch, reported in that sub-batch's word)
+__global__ __launch_bounds__(64) void k_cog_fix(float* out, const int* noff, int D, const uint32_t* flags_dev, uint32_t* user_flags, PackTab pack) {
     const int b = blockIdx.x, o = noff[b], n = noff[b + 1] - o;
-    if (user_flags && b == 0 && threadIdx.x == 0) atomicOr(user_flags, 4u);
+    if (pack.mol_sub) {
+        int k;
+        const bool first = pack_first(pack, noff, b, k);
+        if (!(pack.sub_flags[k] & 4u)) return;
+        if (user_flags && first && threadIdx.x == 0) atomicOr(user_flags + k, 4u);
+    } else {
+        if (!(*flags_dev & 4u)) return;
+        if (user_flags && b == 0 && threadIdx.x == 0) atomicOr(user_flags, 4u);
+    }
     float m[3] = {0.f, 0.f, 0.f};
     for (int i = 0; i < n; ++i) { m[0] += out[(size_t)(o + i) * D]; m[1] += out[(size_t)(o + i) * D + 1]; m[2] += out[(size_t)(o + i) * D + 2]; }
     m[0] /= (float)n; m[1] /= (float)n; m[2] /= (float)n;
@@ -1356,10 +1424,22 @@ __global__ __launch_bounds__(64) void k_sample(StepArgs a) {
     // k_finish's arithmetic, in its order (plans of the sampler are unmasked: mk = 1, cnt = n)
     bool vnan = false;
     float vm[3] = {0.f, 0.f, 0.f};
+    // packed plan: this molecule's sub-batch k, its seed, its first node (the Philox counter starts there), its flag word
+    int k = 0;
+    bool first = b == 0;
+    uint32_t* drift_word = a.flags_dev;
+    if (a.pack.mol_sub) {
+        first = pack_first(a.pack, a.noff, b, k);
+        a.seed = a.pack.seeds[k];
+        a.node_base = 0u - (uint32_t)a.pack.sub_noff[k];
+        drift_word = a.pack.sub_flags + k;
+    }
     if (a.VEL) {
-        const uint32_t fl = *a.flags_dev & ~4u;       // (bit 2 = CoG drift is this launch's own, raised by other workgroups below: k_cog_fix reports it)
+        uint32_t fl = *a.flags_dev;
+        if (a.pack.mol_sub) fl |= a.pack.sub_flags[k];
+        fl &= ~4u;                                    // (bit 2 = CoG drift is this launch's own, raised by other workgroups below: k_cog_fix reports it)
         vnan = (fl & 1u) != 0;
-        if (fl && a.user_flags && b == 0 && threadIdx.x == 0) atomicOr(a.user_flags, fl);
+        if (fl && a.user_flags && first && threadIdx.x == 0) atomicOr(a.user_flags + k, fl);
         // (through LDS: parallel loads, then the serial sum every thread repeats; ns holds >= 3 n floats)
         for (int i = threadIdx.x; i < n; i += 64) { ns[i] = a.VEL[o + i]; ns[n + i] = a.VEL[a.N + o + i]; ns[2 * n + i] = a.VEL[2 * (size_t)a.N + o + i]; }
         __syncthreads();
@@ -1430,7 +1510,7 @@ __global__ __launch_bounds__(64) void k_sample(StepArgs a) {
         float s[3] = {0.f, 0.f, 0.f};
         for (int i = 0; i < n; ++i) { s[0] += ns[i * D] * a.nv0; s[1] += ns[i * D + 1] * a.nv0; s[2] += ns[i * D + 2] * a.nv0; }
         const bool drift = fmaxf(fabsf(s[0]), fmaxf(fabsf(s[1]), fabsf(s[2]))) > 5e-2f;
-        if (drift && threadIdx.x == 0) atomicOr(a.flags_dev, 4u);
+        if (drift && threadIdx.x == 0) atomicOr(drift_word, 4u);
         for (int i = threadIdx.x; i < n; i += 64) {
             float* dst = a.out + (size_t)(o + i) * D;
             const float* src = ns + i * D;

@@ -56,6 +56,7 @@ template <int T>                   // nodes per node tile: 32 (node_tile_x3)
 struct NodeTailRole {
     static_assert(T == 32, "the tail role runs 32-node tiles (64-node tiles cost the edge role a register: gcdm_api.hip, launch of the fused layer)");
     static constexpr bool ON = true;
+    static constexpr bool PACKED = false;              // (a packed plan runs two launches per layer)
     static constexpr int LOG_T = 5;
     static constexpr int SPIN_LIMIT = 1 << 20;          // x ~0.5 us: far beyond any launch; then the flag, never a hang
     struct Args { EdgeMsgX3Args e; TailArgs t; };

@@ -580,7 +580,7 @@ __device__ __forceinline__ void node_tile_x3(const NodeX3Args& ax, char* smem, c
         if (part < 3 && valid) {
             const float v = XP[part * NTP + e] - a.X0[(size_t)part * N + nid];
             a.VEL[(size_t)part * N + nid] = v;
-            if (v != v) atomicOr(a.flags_dev, 1u);
+            if (v != v) raise_nan_vel(a.flags_dev, nid);
             over |= !(fabsf(v) <= 3.0e38f);
         }
     }

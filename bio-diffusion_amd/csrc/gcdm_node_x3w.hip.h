@@ -454,7 +454,7 @@ __device__ __forceinline__ void node_tile_x3w(const NodeX3Args& ax, char* smem, 
         if (part < 3 && valid) {
             const float v = XP[part * TP + e] - a.X0[(size_t)part * N + nid];
             a.VEL[(size_t)part * N + nid] = v;
-            if (v != v) atomicOr(a.flags_dev, 1u);
+            if (v != v) raise_nan_vel(a.flags_dev, nid);
             over |= !(fabsf(v) <= 3.0e38f);
         }
     }

@@ -466,13 +466,20 @@ class _MoleculeGenerationDDPM(nn.Module):
     @torch.inference_mode()
     def sample_and_analyze(self, num_samples: int, node_mask: Optional[torch.Tensor] = None, context: Optional[torch.Tensor] = None,
                            batch_size: Optional[int] = None, max_num_nodes: Optional[int] = 100, num_timesteps: Optional[int] = None,
-                           concurrent_batches: int = 1, **kw) -> Dict[str, Any]:
+                           concurrent_batches: int = 1, packed_batches: Optional[int] = None, **kw) -> Dict[str, Any]:
         """qm9_mol_gen_ddpm.py:747-843 -- the evaluation driver: batches of `batch_size` molecules with sizes drawn from the
         dataset histogram, one 1000-step sampling run per batch, stability statistics.  The per-molecule host loop of the
         reference (`check_molecular_stability` on CPU copies) is one device launch per batch here; only three integers per
         molecule and the atom-type histogram ever leave the GPU.  `concurrent_batches > 1` keeps that many batches in flight on
         separate handles / streams (`mol_gen_sample_concurrent`): same samples, better use of the chip at the reference's batch
-        size of 100.  `save_molecules` (xyz files) is `sample_and_save`."""
+        size of 100.  `packed_batches = K` instead lays K batches end to end in one packed plan on the primary handle
+        (`mol_gen_sample_packed`): the same samples again, without the lane handles; it excludes `concurrent_batches > 1`.
+        `save_molecules` (xyz files) is `sample_and_save`."""
+        if packed_batches is not None:
+            if int(concurrent_batches) > 1:
+                raise ValueError("packed_batches and concurrent_batches > 1 exclude each other: batches are either packed into one plan or run on lane handles")
+            if int(packed_batches) < 1:
+                raise ValueError("packed_batches must be >= 1")
         max_num_nodes = self.dataset_info.get("max_n_nodes", max_num_nodes)
         batch_size = int(cfg_get(self._init_kwargs["dataloader_cfg"], "batch_size", 64)) if batch_size is None else batch_size
         batch_size = min(batch_size, num_samples)
@@ -496,10 +503,15 @@ class _MoleculeGenerationDDPM(nn.Module):
             results.append(check_molecular_stability_batch(xh, atom_types, num_nodes, self.dataset_info))
             type_counts.add_(torch.bincount(atom_types, minlength=self.num_atom_types).cpu())
 
-        K = max(1, int(concurrent_batches))
+        K = max(1, int(concurrent_batches)) if packed_batches is None else int(packed_batches)
         for i0 in range(0, len(plan), K):
             chunk = plan[i0:i0 + K]
-            if K == 1:
+            if packed_batches is not None:
+                outs = self.ddpm.mol_gen_sample_packed([c[1] for c in chunk], self.device, num_timesteps=num_timesteps,
+                                                       contexts=[c[2] for c in chunk], seeds=[1234 + i0 + j for j in range(len(chunk))])
+                for (xh, _, _), c in zip(outs, chunk):
+                    account(xh, c[1])
+            elif K == 1:
                 nb, num_nodes, ctx = chunk[0]
                 xh, _, _ = self.ddpm.mol_gen_sample(num_samples=nb, num_nodes=num_nodes, node_mask=node_mask, context=ctx, device=self.device,
                                                     num_timesteps=num_timesteps, seed=1234 + i0, **kw)

@@ -1310,6 +1310,86 @@ class EquivariantVariationalDiffusion(nn.Module):
         self.last_flags = fl_all
         return results
 
+    @staticmethod
+    def _check_batch_lists(num_nodes_list, contexts, seeds) -> None:
+        """Argument checks of the several-batches drivers that need no device: one context and one seed per batch, no empty batch."""
+        K = len(num_nodes_list)
+        if K == 0:
+            raise ValueError("num_nodes_list is empty: at least one batch is needed")
+        if len(contexts) != K:
+            raise ValueError(f"contexts has {len(contexts)} entries for {K} batches")
+        if len(seeds) != K:
+            raise ValueError(f"seeds has {len(seeds)} entries for {K} batches")
+        for b, nn_ in enumerate(num_nodes_list):
+            if len(nn_) == 0:
+                raise ValueError(f"batch {b} is empty: every batch needs at least one molecule")
+
+    @torch.inference_mode()
+    def mol_gen_sample_packed(self, num_nodes_list: List[torch.Tensor], device: Union[torch.device, str],
+                              num_timesteps: Optional[int] = None, contexts: Optional[List[Optional[torch.Tensor]]] = None,
+                              seeds: Optional[List[int]] = None) -> List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """`mol_gen_sample_concurrent` without the lane handles: the batches are laid end to end in ONE packed plan (`gcdm_plan_batches`) on the primary
+        handle and sampled by one (captured) launch set per step.  Every batch stays a flat batch of its own -- orientation padding at its ends, its own
+        noise stream, its own NaN-in-vel and CoG decisions -- so the results are those of `mol_gen_sample(..., seed=seeds[b])` called one after the other
+        (bit-identical), at one copy of the weights and one workspace."""
+        K = len(num_nodes_list)
+        contexts = contexts if contexts is not None else [None] * K
+        seeds = seeds if seeds is not None else [1234 + b for b in range(K)]
+        self._check_batch_lists(num_nodes_list, contexts, seeds)
+        if bool(getattr(self.dynamics_network, "self_condition", False)):
+            raise NotImplementedError("mol_gen_sample_packed: a self-conditioned model is not served by a packed plan (the self-conditioned step entry points "
+                                      "refuse it); use mol_gen_sample per batch")
+        device = torch.device(device)
+        T = self.T if num_timesteps is None else num_timesteps
+        dyn, lib, h = self._native(device)
+        if dyn.condition_on_context and any(c is None for c in contexts):
+            raise ValueError("context required by a context-conditioned model")
+        sizes = [torch.as_tensor(nn_, dtype=torch.int32, device="cpu").reshape(-1) for nn_ in num_nodes_list]
+        per_batch = torch.tensor([len(sz) for sz in sizes], dtype=torch.int32)
+        nn_all = torch.cat(sizes).contiguous()
+        dyn._plan_key = None                   # the handle's plan is no longer one GCPNetDynamics.plan made: the next plan() call builds its own
+        dyn._plan_src = None
+        _native.check(lib, h, lib.gcdm_plan_batches(h, K, C.c_void_p(per_batch.data_ptr()), C.c_void_p(nn_all.data_ptr())), "gcdm_plan_batches")
+        sd = (C.c_uint64 * K)(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds])
+        _native.check(lib, h, lib.gcdm_set_batch_seeds(h, K, sd), "gcdm_set_batch_seeds")
+        bis = [num_nodes_to_batch_index(len(sz), sz.to(device), device=device) for sz in sizes]
+        node_off = [0]
+        for bi in bis:
+            node_off.append(node_off[-1] + int(bi.shape[0]))
+        N, D = node_off[-1], self.num_x_dims + self.num_node_scalar_features
+        ctx = None
+        if dyn.condition_on_context:
+            ctx = torch.cat([c.to(device, torch.float32)[bi] for c, bi in zip(contexts, bis)], dim=0).contiguous()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())           # noqa: E731
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        z = torch.empty((N, D), dtype=torch.float32, device=device)
+        out = torch.empty((N, D), dtype=torch.float32, device=device)
+        flags = torch.zeros(K, dtype=torch.int32, device=device)
+        no_seed = C.c_uint64(0)                # ignored under a packed plan
+        _native.check(lib, h, lib.gcdm_sample_init(h, ptr(z), None, no_seed, stream), "gcdm_sample_init")
+        for s in reversed(range(T)):
+            _native.check(lib, h, lib.gcdm_sample_step(h, ptr(z), ptr(ctx), s, T, None, no_seed, ptr(flags), stream), "gcdm_sample_step")
+        _native.check(lib, h, lib.gcdm_sample_final(h, ptr(z), ptr(ctx), None, no_seed, ptr(out), ptr(flags), stream), "gcdm_sample_final")
+        words = [int(v) for v in flags.cpu().tolist()]                             # the one host sync of a clean run
+        plan_wide = 0
+        for v in words:
+            plan_wide |= v
+        results, fl_all = [], 0
+        if plan_wide & _native.FLAG_F16_RANGE:     # rare, and plan-wide: redo every batch on the primary handle (which falls back to fp32 MFMA)
+            log.warning("An activation left the f16 range in a packed run; re-running its batches with fp32 MFMA.")
+            if plan_wide & _native.FLAG_TAIL:
+                dyn.disable_fused_layer("mol_gen_sample_packed")
+            for b in range(K):
+                results.append(self.mol_gen_sample(len(sizes[b]), num_nodes_list[b], device, num_timesteps=T, context=contexts[b], seed=seeds[b]))
+                fl_all |= self.last_flags
+            self.last_flags = fl_all
+            return results
+        for b in range(K):
+            fl_all |= self._report_flags(words[b], "mol_gen_sample_packed")
+            results.append((out[node_off[b]:node_off[b + 1]], bis[b], torch.ones_like(bis[b]).bool()))
+        self.last_flags = fl_all
+        return results
+
     def _lane_key(self, device: torch.device):
         dyn = self.dynamics_network
         idx = device.index if device.index is not None else torch.cuda.current_device()

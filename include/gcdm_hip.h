@@ -92,6 +92,28 @@ int gcdm_plan_batch(gcdm_handle* h, int32_t num_molecules, const int32_t* host_n
  * an error (the reference's sampling drivers always pass an all-True mask, src/mol_gen_sample.py:160). */
 int gcdm_plan_batch_masked(gcdm_handle* h, int32_t num_molecules, const int32_t* num_nodes, const uint8_t* node_mask);
 
+/* Packed plan: num_batches independent flat batches ("sub-batches") laid end to end in ONE plan and served by one launch set per call -- the evaluation
+ * driver's flat batches of 100 molecules (qm9_mol_gen_ddpm.py:747-843) without one handle per batch.  molecules_per_batch host [num_batches] (each >= 1),
+ * num_nodes host [sum molecules_per_batch] = the concatenation of the sub-batches' molecule sizes.  Nodes, CSR offsets and tile lists are those of
+ * gcdm_plan_batch on the concatenation, except that the edges of every sub-batch start on a 64-edge boundary of the flat edge list (a row cut by a tile boundary
+ * is summed from per-tile partial sums, so where the boundaries fall decides the last bits; the slots in between belong to no row; gcdm_num_edges does not count
+ * them); device tables add the sub-batch of each molecule and the first node of each sub-batch.  Every sub-batch stays a flat
+ * batch of its own: its orientations are zero padded at ITS two ends (protein_graph_dataset.py:217-225), a NaN in vel zeroes the vel of ITS nodes
+ * (gcpnet.py:1212-1220 is per call), the CoG re-projection is ITS decision (variational_diffusion.py:1389-1402), its Philox noise is counted from ITS first
+ * node with ITS seed.  Sub-batch k of a packed run is bit-identical to the same batch planned with gcdm_plan_batch and run with seed = seeds[k]
+ * (num_batches == 1: to gcdm_plan_batch in every output).  Under a packed plan
+ *   - gcdm_forward, gcdm_sample_init, gcdm_sample_step, gcdm_sample_step_to and gcdm_sample_final work on all sub-batches at once; their scalar `seed` argument
+ *     is IGNORED (the seeds are the table of gcdm_set_batch_seeds); `flags`, when given, points at num_batches words (word k: GCDM_FLAG_NAN_VEL and
+ *     GCDM_FLAG_COG_DRIFT of sub-batch k; GCDM_FLAG_F16_RANGE and GCDM_FLAG_TAIL are plan-wide and OR-ed into every word); a `noise` tape stays [N,3+F] in flat
+ *     order and `context` stays per node; the captured step (option "step_graph") serves it: seeds and tables live at device addresses that hold as long as the plan;
+ *   - the _sc entry points, the inpaint entry points, gcdm_encode_samples, gcdm_plan_batch_masked with a mask and a non-zero value of the options "fix_noise",
+ *     "flat_prev", "flat_next", "node_base" return an error and leave the handle and its plan as they were; a self-conditioned handle, or one on which one of those
+ *     options is non-zero, cannot be given a packed plan.
+ * gcdm_plan_batch replaces a packed plan by an ordinary one.  gcdm_get_option("num_batches"): num_batches of a packed plan, 0 otherwise. */
+int gcdm_plan_batches(gcdm_handle* h, int32_t num_batches, const int32_t* molecules_per_batch, const int32_t* num_nodes);
+/* Philox seeds of the sub-batches of the current packed plan, host [num_batches] (all 0 after gcdm_plan_batches).  Synchronises the device. */
+int gcdm_set_batch_seeds(gcdm_handle* h, int32_t num_batches, const uint64_t* host_seeds);
+
 /* One epsilon prediction.  xh [N,3+F] device, t [N] device (the reference passes [N,1]), context [N,C] device or
  * NULL, out [N,3+F] device, flags: device uint32 (OR-ed into) or NULL.  node_mask is all-True (mol_gen_sample.py:160).
  * Replaces GCPNetDynamics.forward (gcpnet.py:1042-1052, 1069-1232). */
