@@ -19,7 +19,7 @@ from .variational_diffusion import EquivariantVariationalDiffusion, PredefinedNo
 from .mol_gen_ddpm import QM9MoleculeGenerationDDPM, GEOMMoleculeGenerationDDPM, sample_sweep_conditionally  # noqa: F401
 from . import _native, stability, xyz, sdf                                      # noqa: F401
 from . import optim                                                              # noqa: F401
-from .optim import TrainingUpdate                                                # noqa: F401
+from .optim import TrainingUpdate, BucketedUpdate                                # noqa: F401
 from . import classifier                                                         # noqa: F401
 from .classifier import EGNN, get_classifier, property_mae                       # noqa: F401
 from .sdf import write_sdf_file, build_molecules, bond_order_matrices, Molecule  # noqa: F401
@@ -33,5 +33,5 @@ __all__ = [
     "QM9MoleculeGenerationDDPM", "GEOMMoleculeGenerationDDPM",
     "check_molecular_stability", "check_molecular_stability_batch", "get_bond_length_arrays", "CategoricalDistribution",
     "save_xyz_file", "write_xyz_file", "write_sdf_file", "build_molecules", "bond_order_matrices", "Molecule", "F16RangeError",
-    "optim", "TrainingUpdate", "classifier", "EGNN", "get_classifier", "property_mae",
+    "optim", "TrainingUpdate", "BucketedUpdate", "classifier", "EGNN", "get_classifier", "property_mae",
 ]

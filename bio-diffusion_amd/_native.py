@@ -23,7 +23,8 @@ OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(
                os.path.join(_HERE, "csrc", "gcdm_ops.gcp2.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_gcp2_train.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.classifier.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier.h"),
-               os.path.join(_HERE, "csrc", "gcdm_ops.objective.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_objective.h")]
+               os.path.join(_HERE, "csrc", "gcdm_ops.objective.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_objective.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.bucket.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_grad_bucket.h")]
 ABI_VERSION = 2
 
 FLAG_NAN_VEL, FLAG_MEAN_NOT_ZERO, FLAG_COG_DRIFT, FLAG_F16_RANGE = 1, 2, 4, 8
@@ -184,6 +185,14 @@ OBJECTIVE_RESTYPES = {"gcdm_objective_workspace_bytes": C.c_int64}
 OBJECTIVE_MAX_TYPES = 16                                                  # GCDM_OBJECTIVE_MAX_TYPES
 OBJECTIVE_TRAIN_VLB, OBJECTIVE_EVAL, OBJECTIVE_TRAIN_L2 = 0, 1, 2         # GCDM_OBJECTIVE_*
 OBJECTIVE_FLAG_UNSORTED, OBJECTIVE_FLAG_SIZE, OBJECTIVE_FLAG_T_RANGE, OBJECTIVE_FLAG_EMPTY = 1, 2, 4, 8
+# the flat gradient bucket of data-parallel / accumulated training steps (include/gcdm_grad_bucket.h), exported from the same library
+GRAD_BUCKET_SIGNATURES = {
+    "gcdm_grad_bucket_floats": [I64, I64],
+    "gcdm_grad_bucket_pack": [P, P, P, I64, I64, I64, I32, D, I32, P],
+    "gcdm_grad_bucket_check": [P, P, I64, I64, I64, I32, I32, P],
+}
+GRAD_BUCKET_RESTYPES = {"gcdm_grad_bucket_floats": C.c_int64}
+GRAD_BUCKET_FLAG_MISMATCH = 2   # GCDM_GRAD_BUCKET_FLAG_MISMATCH
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -195,10 +204,10 @@ def load_ops() -> C.CDLL:
     if not os.path.exists(OPS_LIB_PATH):
         raise RuntimeError(f"{OPS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
     lib = C.CDLL(OPS_LIB_PATH)
-    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(GCP2_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()):
+    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(GCP2_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(GRAD_BUCKET_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = sig
-        fn.restype = {**MP_TRAIN_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES}.get(name, C.c_int)
+        fn.restype = {**MP_TRAIN_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
     _ops_lib = lib
     return lib
 

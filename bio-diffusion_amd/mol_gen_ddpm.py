@@ -247,6 +247,14 @@ class _MoleculeGenerationDDPM(nn.Module):
         return TrainingUpdate(self.parameters(), lr=1e-4, weight_decay=1e-12, amsgrad=True, clip_gradients=clip, queue_len=50,
                               ema_decay=0.9999, ema_every=1, ema_start=0)
 
+    def configure_data_parallel(self, group=None, accumulate_grad_batches: int = 1):
+        """Opt-in: a fresh ``configure_optimizers()`` wrapped for data-parallel and accumulated steps (optim.BucketedUpdate) -- the
+        reference's ``strategy: ddp_find_unused_parameters_false`` and ``accumulate_grad_batches`` (configs/trainer/default.yaml).  Call
+        ``accumulate()`` after each ``backward()`` and ``step()`` after every ``accumulate_grad_batches``-th; with a process group, bring the
+        replicas to one state first (parallel.broadcast_training_state).  Without one it runs as a single rank."""
+        from .optim import BucketedUpdate
+        return BucketedUpdate(self.configure_optimizers(), group=group, accumulate_grad_batches=accumulate_grad_batches)
+
     @torch.inference_mode()
     def validation_step(self, batch: Any, batch_idx: int = 0, **kw) -> Dict[str, Any]:
         """The metrics dictionary of the reference's validation / test step (without the Lightning logging around it)."""

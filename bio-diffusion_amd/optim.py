@@ -5,7 +5,11 @@ AMSGrad (configs/model/*_mol_gen_ddpm.yaml) and the EMA of the weights (configs/
 One ``step()`` is three launches on the current stream and no host sync.  Parameters stay where they are and autograd keeps ``p.grad``;
 the moments, the AMSGrad maximum and the EMA live in one flat fp32 buffer.  Deliberate difference from the reference: a step whose gradient
 norm is not finite is skipped as a whole (parameters, moments, step counts, EMA and queue unchanged) and raises FLAG_NONFINITE in
-``read_flags()``; the reference would write NaN into every weight."""
+``read_flags()``; the reference would write NaN into every weight.
+
+``BucketedUpdate`` (opt-in) wraps a ``TrainingUpdate`` for data-parallel and accumulated steps: every backward pass is packed into one flat
+gradient bucket laid out like the update's state (include/gcdm_grad_bucket.h), one all-reduce sums it over the ranks, and the same fused
+step consumes it."""
 from __future__ import annotations
 
 import contextlib
@@ -17,6 +21,7 @@ import torch
 from . import _native
 
 FLAG_NONFINITE = _native.OPTIM_FLAG_NONFINITE
+FLAG_MISMATCH = _native.GRAD_BUCKET_FLAG_MISMATCH       # BucketedUpdate: the ranks disagreed on which tensors have a gradient
 QUEUE_MAX = _native.OPTIM_QUEUE_MAX
 CHUNK = 16384                 # values per chunk (one workgroup each): the QM9 model gives several hundred chunks
 QUEUE_SEED = 3000.0           # qm9_mol_gen_ddpm.py: gradnorm_queue.add(3000), a large value that gets flushed
@@ -139,7 +144,8 @@ class TrainingUpdate(torch.optim.Optimizer):
         if [p.data_ptr() for p in ps] != self._param_ptrs:
             raise RuntimeError("a parameter of TrainingUpdate was re-allocated (e.g. module.to() after construction): build the update again")
 
-    def _refresh_grads(self):
+    def _grad_pointers(self) -> List[int]:
+        """The device pointer of every ``p.grad`` as the kernels take it, 0 where there is none."""
         ps = self.param_groups[0]["params"]
         ptrs = []
         for i, p in enumerate(ps):
@@ -150,6 +156,10 @@ class TrainingUpdate(torch.optim.Optimizer):
             if g.is_sparse or g.dtype != torch.float32 or g.device != self._dev or g.shape != p.shape or not g.is_contiguous():
                 raise ValueError(f"gradient of parameter {i} is not a dense contiguous fp32 tensor on {self._dev}")
             ptrs.append(g.data_ptr())
+        return ptrs
+
+    def _refresh_grads(self):
+        ptrs = self._grad_pointers()
         if ptrs != self._grad_ptrs:
             src = torch.tensor(ptrs, dtype=torch.int64).pin_memory()
             self._view(_GTAB, torch.int64, self._T).copy_(src, non_blocking=True)
@@ -314,3 +324,137 @@ class TrainingUpdate(torch.optim.Optimizer):
                     self._param_view(3, t).copy_(ema[t])
             else:
                 self._swap(1)
+
+
+class BucketedUpdate:
+    """Data-parallel and accumulated training steps on one flat gradient bucket (include/gcdm_grad_bucket.h), around an unchanged
+    ``TrainingUpdate``.  Opt-in: nothing here runs unless it is constructed.
+
+        upd = model.configure_data_parallel(group=None, accumulate_grad_batches=k)
+        for micro_batch in ...:
+            model.training_step(micro_batch)["loss"].backward(); upd.accumulate(); upd.zero_grad()
+            # after every k-th micro-batch:
+            upd.step()
+
+    ``accumulate()`` adds ``p.grad / (world * accumulate_grad_batches)`` of every parameter to the bucket in one launch; ``step()`` sums the
+    bucket over the ranks of ``group`` with one ``all_reduce`` (none without an initialised process group, or with one rank), checks that the
+    ranks agree on which tensors have a gradient, and lets the wrapped update take its step on the bucket: the clipping norm is the norm of
+    the averaged gradient, as under the reference's DDP strategy, so every rank pushes the same value onto its queue and the replicas stay
+    bit-identical.  The reduce is not overlapped with the backward pass, and no multi-GPU scaling has been measured.
+
+    Loss semantics are DDP's and Lightning's: each micro-batch of each rank contributes the gradient of its own ``nll.mean(0)``, and the
+    step sees the mean of those means.  With shards or micro-batches of unequal size that is not the mean over all molecules -- exactly as
+    in the reference.
+
+    When the ranks disagree on a tensor's presence (one has a gradient, another has none) the step is skipped as a whole on every rank and
+    ``read_flags()`` carries ``FLAG_MISMATCH`` (together with ``FLAG_NONFINITE``, the mechanism of the skip).  A tensor counts as present on
+    this rank when any of the step's passes had a gradient for it.  Everything else -- ``zero_grad``, ``param_groups``, ``queue``,
+    ``ema_weights`` ... -- is the wrapped update's."""
+
+    def __init__(self, update: TrainingUpdate, group=None, accumulate_grad_batches: int = 1):
+        if not isinstance(update, TrainingUpdate):
+            raise TypeError("BucketedUpdate wraps an optim.TrainingUpdate")
+        if int(accumulate_grad_batches) != accumulate_grad_batches or int(accumulate_grad_batches) < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
+        self.update = update
+        self.group = group
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self._passes = 0
+        self._bucket: Optional[torch.Tensor] = None
+
+    def __getattr__(self, name):
+        if name == "update":
+            raise AttributeError(name)
+        return getattr(self.update, name)
+
+    # ---- the bucket ------------------------------------------------------------------------------------------------------------
+    def _world(self) -> int:
+        import torch.distributed as dist
+        return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
+
+    def _alloc(self):
+        u = self.update
+        n = int(u._lib.gcdm_grad_bucket_floats(u._total, u._T))
+        assert n >= u._total + u._T
+        self._bucket = torch.empty(n, dtype=torch.float32, device=u._dev)
+        assert self._bucket.data_ptr() % 256 == 0
+        self._gtab = torch.zeros(u._T, dtype=torch.int64, device=u._dev)
+        self._ptrs: Optional[List[int]] = None
+        self._have = [False] * u._T                  # tensors with a gradient in a pass of the current step
+        self._views: List[Optional[torch.Tensor]] = [None] * u._T
+
+    @property
+    def bucket(self) -> torch.Tensor:
+        """The flat bucket: ``total`` values laid out like a state quarter of the update, then the presence tail.  Before ``step()`` it holds
+        this rank's scaled sum, after it the sum over the ranks."""
+        if self._bucket is None:
+            self._alloc()
+        return self._bucket
+
+    def _call(self, name, *args):
+        st = getattr(self.update._lib, name)(*args)
+        if st != 0:
+            raise _native.NativeError(f"{name} failed ({st})")
+
+    @torch.no_grad()
+    def accumulate(self) -> None:
+        """After each micro-batch's ``backward()``: one launch, no host sync."""
+        if self._passes >= self.accumulate_grad_batches:
+            raise RuntimeError(f"accumulate() was called {self._passes} times with accumulate_grad_batches={self.accumulate_grad_batches}: step() is due")
+        u = self.update
+        bucket = self.bucket
+        u._check_params()
+        ptrs = u._grad_pointers()
+        if ptrs != self._ptrs:
+            self._gtab.copy_(torch.tensor(ptrs, dtype=torch.int64).pin_memory(), non_blocking=True)
+            self._ptrs = ptrs
+        first = self._passes == 0
+        self._have = [p != 0 or (h and not first) for p, h in zip(ptrs, self._have)]
+        scale = 1.0 / (self._world() * self.accumulate_grad_batches)
+        self._call("gcdm_grad_bucket_pack", C.c_void_p(u._ws.data_ptr()), C.c_void_p(self._gtab.data_ptr()), C.c_void_p(bucket.data_ptr()),
+                   u._total, u._T, u._C, u.param_groups[0]["queue_len"], scale, int(first), u._stream())
+        self._passes += 1
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        """All-reduce, presence check, then ``TrainingUpdate.step()`` reading its gradients from the bucket (``p.grad`` is left as it was)."""
+        if closure is not None:
+            raise ValueError("BucketedUpdate.step takes no closure: run the passes and accumulate() yourself")
+        if self._passes < self.accumulate_grad_batches:
+            raise RuntimeError(f"step() after {self._passes} of {self.accumulate_grad_batches} accumulate() calls")
+        u = self.update
+        world = self._world()
+        if world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(self._bucket, op=dist.ReduceOp.SUM, group=self.group)
+        self._call("gcdm_grad_bucket_check", C.c_void_p(u._ws.data_ptr()), C.c_void_p(self._bucket.data_ptr()), u._total, u._T, u._C,
+                   u.param_groups[0]["queue_len"], world, u._stream())
+        # the update reads p.grad: for the length of its step that is the tensor's segment of the bucket.  Its gradient table (section 2) is
+        # thereby written once, and again only when the set of present tensors changes
+        ps = u.param_groups[0]["params"]
+        saved = [p.grad for p in ps]
+        try:
+            for t, p in enumerate(ps):
+                if self._have[t]:
+                    if self._views[t] is None:
+                        o = u._offset[t]
+                        self._views[t] = self._bucket[o: o + u._numel[t]].view_as(p)
+                    p.grad = self._views[t]
+                else:
+                    p.grad = None
+            u.step()
+        finally:
+            for p, g in zip(ps, saved):
+                p.grad = g
+        self._passes = 0
+
+    def read_flags(self, reset: bool = True) -> int:
+        """The wrapped update's flag word: FLAG_NONFINITE (a step was skipped) and FLAG_MISMATCH (it was skipped because the ranks disagreed
+        on which tensors have a gradient)."""
+        return self.update.read_flags(reset)
+
+    def state_dict(self) -> Dict[str, Any]:
+        return self.update.state_dict()
+
+    def load_state_dict(self, state_dict: Dict[str, Any]) -> None:
+        self.update.load_state_dict(state_dict)

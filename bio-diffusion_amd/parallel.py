@@ -5,10 +5,13 @@ per rank (one process per GPU, ``torch.distributed`` backend "nccl" = RCCL over 
 There is no collective inside the 1000-step loop; the only communication is one gather of the final samples.
 Parity definition: the N-rank result equals N independent single-GPU runs of the shards (each shard is its own flat
 batch -- the flat-batch orientation quirk, SURVEY A.6.2, is defined per flat batch).
+
+Training (opt-in, optim.BucketedUpdate): ``shard_batch`` cuts a training batch the same way, ``broadcast_training_state`` brings the
+replicas to one state as DDP does at construction, and the only collective of a step is one all-reduce of the flat gradient bucket.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import Any, List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -70,3 +73,59 @@ def sample_sharded(ddpm, num_nodes: torch.Tensor, device, context: Optional[torc
     if world == 1:
         return xh, torch.as_tensor(local).to(torch.int64)
     return gather_samples(xh, torch.as_tensor(local), group)
+
+
+def shard_batch(batch, rank: int, world_size: int):
+    """The contiguous block of molecules ``shard_range`` gives ``rank``, cut out of a training batch (a mapping with the per-node ``batch``
+    index, molecules in ascending order): per-node tensors keep the block's rows, ``batch`` is re-based to start at 0, tensors with one row
+    per molecule keep rows lo .. hi, ``num_graphs`` becomes the block's size; everything else is passed on.  Returns the same mapping type."""
+    bi = batch["batch"]
+    N = bi.shape[0]
+    B = int(batch["num_graphs"]) if batch.get("num_graphs") is not None else int(bi.max().item()) + 1
+    lo, hi = shard_range(B, rank, world_size)
+    rows = (bi >= lo) & (bi < hi)
+    out = type(batch)()
+    for k, v in batch.items():
+        if k == "batch":
+            out[k] = v[rows] - lo
+        elif k == "num_graphs" and v is not None:
+            out[k] = hi - lo
+        elif torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == N:
+            out[k] = v[rows]
+        elif torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B:
+            out[k] = v[lo:hi]
+        elif isinstance(v, dict):
+            out[k] = {kk: (vv[rows] if torch.is_tensor(vv) and vv.dim() >= 1 and vv.shape[0] == N else vv) for kk, vv in v.items()}
+        else:
+            out[k] = v
+    return out
+
+
+@torch.no_grad()
+def broadcast_training_state(model: torch.nn.Module, update: Any, src: int = 0, group: Optional[dist.ProcessGroup] = None) -> None:
+    """What DDP does at construction, for the fused update too: every rank takes rank ``src``'s parameters and buffers and the update's
+    flat state (moments, AMSGrad maximum, EMA), gradient-norm queue, scalar block and step counts.  ``update``: an optim.TrainingUpdate or
+    the optim.BucketedUpdate around one.  ``src`` is a global rank, as for ``dist.broadcast``.  Without an initialised process group there
+    is nothing to do."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return
+    from . import optim
+    upd = update.update if isinstance(update, optim.BucketedUpdate) else update
+    params = [p for p in model.parameters()]
+    by_kind = {}
+    for p in params:
+        by_kind.setdefault((p.dtype, p.device), []).append(p)
+    for ps in by_kind.values():                                   # one collective per dtype, not one per tensor
+        flat = torch.cat([p.detach().reshape(-1) for p in ps])
+        dist.broadcast(flat, src, group=group)
+        o = 0
+        for p in ps:
+            p.copy_(flat[o: o + p.numel()].view_as(p))
+            o += p.numel()
+    for b in model.buffers():
+        dist.broadcast(b, src, group=group)
+    dist.broadcast(upd._state, src, group=group)
+    owned = upd._ws[upd._off[optim._STEPS] // 8:]                 # the device-owned sections: step counts, scratch, queue, scalar block
+    dist.broadcast(owned, src, group=group)
+    upd._scal_host.copy_(upd._scal().cpu())
+    upd._scal_pending = False
