@@ -25,22 +25,31 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
-struct LayerDev {
-    // edge kernel
-    const v4f* w0; int G0; const float* wddE; const v4f* wg0; const float* bg0; const float* wup0;
-    GcpW mk[3];
-    const float* wa; float ba;
-    // node kernel
-    GcpW ff, pos;
+// The node-level halves of a layer's msg0, which the node stage in front of it (the previous layer's, or the embedding's) computes
+struct NextMsg0 {
     const v4f* wpq; const float* bpq; const float* wddI; const float* wddJ;
-    // split-precision (f16 x3) images of the edge-kernel GEMM weights
-    const h8 *w0H, *w0L, *wg0H, *wg0L, *wH[3], *wL[3], *wgH[3], *wgL[3], *wbeH, *wbeL;
-    const h8 *vpH[3], *vpL[3], *vf1[3], *vf2[3], *vf0H, *vf0L;   // vector path on the matrix pipe (gcdm_edge_x3.hip.h)
-    const h8 *vdH, *vdL;
-    const float *bpqx, *wax;       // scaled units of the split-precision edge kernel: c * bias of the msg0 node halves, attention weights / c
-    int KB0, KB;
+    const h8 *wpqH, *wpqL, *vdH, *vdL;    // split-precision images of c * (P | Q) and of [wddI; wddJ]
+    const float* bpqx;                    // c * bias (scaled units of the split-precision edge kernel)
+};
+
+// One interaction layer as the kernels take it: Pool::add fills the weight members at finalize, forward_impl copies `edge` and adds the plan's and the call's part
+struct LayerDev {
+    EdgeMsgX3Args edge;            // edge.base is the fp32 kernel's EdgeMsgArgs; buffers, sizes, pool bounds and the schedule are null / 0 here
+    GcpX3 mkx[3];                  // generic images of msg1..3: in the pool, read by no kernel (the edge kernel has its own K order, edge.wH / wL)
+    GcpW ff, pos;
     GcpX3 ffx, posx;
-    const h8 *wpqH, *wpqL;
+    NextMsg0 next;
+};
+
+// Everything gcdm_finalize_weights derives from the host weights: one object, so that a packing pass can build it beside the handle's and swap it in
+struct ModelDev {
+    std::vector<LayerDev> layers;
+    GcpW emb{}, proj{};
+    GcpX3 embx{}, projx{};
+    // edge embedding: fp32 tables (.1: second coefficient set of self-conditioning), split-precision A operands of k_edge_embed_x3
+    const float *ee_ws = nullptr, *ee_bs = nullptr, *ee_wd = nullptr, *ee_wdf = nullptr, *ee_kappa = nullptr, *ee_wg = nullptr, *ee_bg = nullptr;
+    const float *ee_wd1 = nullptr, *ee_wdf1 = nullptr, *ee_kappa1 = nullptr;
+    const h8 *ee_xwH = nullptr, *ee_xwL = nullptr, *ee_xgH = nullptr, *ee_xgL = nullptr;
 };
 
 }  // namespace
@@ -53,16 +62,11 @@ struct gcdm_handle {
     // derived dims
     int F = 0, C = 0, Fin = 0, FinG = 0, D = 0, Se = 0, Ve = 0, L = 0, H0 = 0;
     int sc = 0, FinP = 0;            // self-conditioning: Fin = [h | h_sc | t | ctx] feeds the node embedding, FinP = F + 1 + C is what the projection returns
-    const float *ee_wd1 = nullptr, *ee_wdf1 = nullptr, *ee_kappa1 = nullptr;
-    const h8 *ee_xwH = nullptr, *ee_xwL = nullptr, *ee_xgH = nullptr, *ee_xgL = nullptr;     // split-precision A operands of k_edge_embed_x3
     float *X0SC = nullptr, *BL = nullptr, *USC = nullptr;
     // device weights
     float* wpool = nullptr;
     size_t wpool_bytes = 0;
-    std::vector<LayerDev> layers;
-    GcpW emb{}, proj{};
-    GcpX3 embx{}, projx{};
-    const float *ee_ws = nullptr, *ee_bs = nullptr, *ee_wd = nullptr, *ee_wdf = nullptr, *ee_kappa = nullptr, *ee_wg = nullptr, *ee_bg = nullptr;
+    ModelDev m;                      // pointers into wpool
     std::vector<float> gamma;
     // plan
     int B = 0, N = 0, max_n = 0;
@@ -76,8 +80,10 @@ struct gcdm_handle {
     float *PQ4b = nullptr, *VDIb = nullptr, *VDJb = nullptr;   // second set of the node-level msg0 halves: layer l gathers set l & 1, its node tiles write set (l + 1) & 1 (round 6:
                                                                // with the node tiles as a tail role of the edge workgroups both happen in ONE launch)
     // Fused layer launch (gcdm_layer_x3.hip.h): table of the node-tile queue (TailArgs::tab; null when the plan does not qualify) and its counters
-    int* d_tail_tab = nullptr;                     // per XCD [8 x + 0..3]: first owned node tile, owned node tiles, (unused), rel_node_end | [64 + t]: need[node tile t]
-    int* d_tail_ctr = nullptr;                     // ready[node tiles of 32] | qcur[TAIL_CTR_WORDS]  (zeroed at plan time, self-resetting)
+    int* d_tail_tab = nullptr;                     // XCD x [8 x + 0..3]: first owned node tile, owned node tiles, edge tiles + owned node tiles (not read), rel_node_end |
+                                                   // [64 + t]: edge tiles node tile t waits for, | 1 << 16 when they reach into the next XCD's range (TailArgs::tab)
+    int* d_tail_ctr = nullptr;                     // ready[tail_tiles32] | qcur[TAIL_CTR_WORDS = 25]: queue cursors [0..7], workgroups that left [8], xcc_seen [9..16],
+                                                   // arrivals [17..24]  (zeroed at plan time, self-resetting; TailArgs::ready / qcur)
     int tail_tiles32 = 0;
     int fuse_node = 1;               // option "fuse_node" / env GCDM_FUSE_NODE: 1 = the layer's node tiles run as a tail role of the persistent edge workgroups (one launch
                                      // per layer) where the plan qualifies; 0 = two launches per layer (rounds 1-5)
@@ -192,13 +198,23 @@ struct DeviceGuard {
 };
 
 // ---- pool builder: 16-byte aligned sub-arrays of one device allocation ---------------------------
+// add() copies an array into the host image and notes the pointer that is to address it; resolve() patches the noted pointers once the image is on
+// the device.  The slots must stay where they are in between.
 struct Pool {
     std::vector<float> host;
-    size_t add(const std::vector<float>& a) {
-        size_t off = (host.size() + 3) & ~size_t(3);
+    std::vector<std::pair<void*, size_t>> slots;          // (address of a `const T*`, offset in floats)
+    template <class T>
+    void add(const std::vector<float>& a, const T** slot) {
+        const size_t off = (host.size() + 3) & ~size_t(3);
         host.resize(off + a.size(), 0.f);
         std::memcpy(host.data() + off, a.data(), a.size() * sizeof(float));
-        return off;
+        slots.push_back({slot, off});
+    }
+    void resolve(const float* base) {
+        for (const auto& s : slots) {
+            const float* p = base + s.second;
+            std::memcpy(s.first, &p, sizeof p);           // every slot is an object pointer: same representation as const float*
+        }
     }
 };
 
@@ -237,6 +253,13 @@ void split_f16(float x, uint16_t& hi, uint16_t& lo) {
     std::memcpy(&lo, &l, 2);
 }
 
+// f16 pairs as the pool's 32-bit words
+std::vector<float> f16_words(const std::vector<uint16_t>& v) {
+    std::vector<float> o(v.size() / 2);
+    std::memcpy(o.data(), v.data(), v.size() * 2);
+    return o;
+}
+
 void pack_x3(Dense& W, std::vector<float>& outH, std::vector<float>& outL) {
     const int MT = W.M / 32, KB = W.K / 16;
     std::vector<uint16_t> H((size_t)W.M * W.K), L((size_t)W.M * W.K);
@@ -247,10 +270,8 @@ void pack_x3(Dense& W, std::vector<float>& outH, std::vector<float>& outL) {
                     const size_t o = (((size_t)mt * KB + kb) * 64 + lane) * 8 + s;
                     split_f16(W.at(32 * mt + (lane & 31), 16 * kb + 8 * (lane >> 5) + s), H[o], L[o]);
                 }
-    outH.assign(H.size() / 2, 0.f);
-    outL.assign(L.size() / 2, 0.f);
-    std::memcpy(outH.data(), H.data(), H.size() * 2);
-    std::memcpy(outL.data(), L.data(), L.size() * 2);
+    outH = f16_words(H);
+    outL = f16_words(L);
 }
 
 // gate weights for the in-register contraction: block (mt, j) slot s of lane l  <->  channel 32 mt + 16 j + 8 (s >> 2) + 4 (l >> 5) + (s & 3)
@@ -263,10 +284,8 @@ void pack_gate_x3(Dense& Wg /*[32][256]*/, std::vector<float>& outH, std::vector
                     const size_t o = (((size_t)mt * 2 + j) * 64 + lane) * 8 + s;
                     split_f16(Wg.at(lane & 31, 32 * mt + 16 * j + 8 * (s >> 2) + 4 * (lane >> 5) + (s & 3)), H[o], L[o]);
                 }
-    outH.assign(H.size() / 2, 0.f);
-    outL.assign(L.size() / 2, 0.f);
-    std::memcpy(outH.data(), H.data(), H.size() * 2);
-    std::memcpy(outL.data(), L.data(), L.size() * 2);
+    outH = f16_words(H);
+    outL = f16_words(L);
 }
 
 struct WView {
@@ -281,11 +300,6 @@ struct WView {
 // (the constant itself: X3_C in gcdm_edge_x3.hip.h)
 
 // ---- A operands of the vector path (v_mfma_f32_16x16x32_f16: lane l holds row l & 15, k = 8 (l >> 4) + j), see gcdm_edge_x3.hip.h ----
-std::vector<float> f16_words(const std::vector<uint16_t>& v) {
-    std::vector<float> o(v.size() / 2);
-    std::memcpy(o.data(), v.data(), v.size() * 2);
-    return o;
-}
 
 // [W_down (H = 8 rows); W_frames (3 rows)] x 32 channels.  MFMA row 4q + i = hidden vector 3q + i (i < 3, real while < 8) or frame vector q
 // (i = 3, q < 3), so that every lane class q of the D layout runs the same code; k = 8q + j <-> channel (j < 4 ? 4q + j : 16 + 4q + j - 4)
@@ -379,19 +393,9 @@ std::vector<float> padded(const WView& w, int n) {
 
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-// Pending pointer fix-ups (offsets into the pool until it is uploaded)
-struct GcpOff {
-    size_t w = 0, b = 0, w2 = 0, b2 = 0, wdd = 0, wg = 0, bg = 0, wup = 0;
-    bool has_w2 = false, has_gate = false;
-    int G = 0, H = 0, V_in = 0, V_out = 0;
-    size_t xwH = 0, xwL = 0, xw2H = 0, xw2L = 0, xwgH = 0, xwgL = 0;   // split-precision images
-    size_t xvmH = 0, xvmL = 0; bool has_vm = false;
-    int KB = 0;
-};
-
 // generic GCP2 (scalar input = s_in channels laid out in 4-groups starting at K' = 0)
 bool build_gcp(gcdm_handle* h, Pool& pool, const std::string& pre, int s_in, int v_in, int s_out, int v_out, int bottleneck,
-               bool ff, GcpOff& o) {
+               bool ff, GcpW& g, GcpX3& x) {
     const int H = bottleneck > 1 ? v_in / bottleneck : std::max(v_in, v_out);
     const int SIg = (s_in + 3) / 4, Hg = (H + 3) / 4;
     const int Kp = round_up(4 * (SIg + Hg + 3), 8), Mp = round_up(s_out, 32);
@@ -406,9 +410,9 @@ bool build_gcp(gcdm_handle* h, Pool& pool, const std::string& pre, int s_in, int
         for (int k = 0; k < H; ++k) W.at(m, 4 * SIg + k) = ws.at(m, s_in + k);
         for (int k = 0; k < 9; ++k) W.at(m, 4 * (SIg + Hg) + k) = ws.at(m, s_in + H + k);
     }
-    o.w = pool.add(pack_mfma(W));
-    o.b = pool.add(padded(bs, Mp));
-    o.G = Kp / 8; o.H = H; o.V_in = v_in; o.V_out = v_out;
+    pool.add(pack_mfma(W), &g.w);
+    pool.add(padded(bs, Mp), &g.b);
+    g.G = Kp / 8; g.H = H; g.V_in = v_in; g.V_out = v_out;
     {   // split-precision image: K' = [s_in -> 8-groups | n (H -> 8-groups) | q (9 -> 16)] padded to a multiple of 16
         const int S8 = (s_in + 7) / 8, H8 = (H + 7) / 8;
         const int Kx = round_up(8 * (S8 + H8 + 2), 16);
@@ -420,28 +424,27 @@ bool build_gcp(gcdm_handle* h, Pool& pool, const std::string& pre, int s_in, int
         }
         std::vector<float> xh, xl;
         pack_x3(Wx, xh, xl);
-        o.xwH = pool.add(xh); o.xwL = pool.add(xl); o.KB = Kx / 16;
+        pool.add(xh, &x.wH); pool.add(xl, &x.wL); x.KB = Kx / 16;
     }
     std::vector<float> dd((size_t)(H + 3) * v_in);
     for (int r = 0; r < H; ++r) for (int c = 0; c < v_in; ++c) dd[(size_t)r * v_in + c] = wd.at(r, c);
     for (int r = 0; r < 3; ++r) for (int c = 0; c < v_in; ++c) dd[(size_t)(H + r) * v_in + c] = wdf.at(r, c);
-    o.wdd = pool.add(dd);
+    pool.add(dd, &g.wdd);
     if (v_in % 32 == 0) {            // vector pre-phase on the matrix pipe (node kernels)
         std::vector<float> a, b;
         pack_vecmat(dd, H + 3, v_in, a, b);
-        o.xvmH = pool.add(a); o.xvmL = pool.add(b); o.has_vm = true;
+        pool.add(a, &x.vmH); pool.add(b, &x.vmL);
     }
     if (ff) {
         WView w2, b2;
         if (!get_w(h, pre + "scalar_out.2.weight", s_out, s_out, w2) || !get_w(h, pre + "scalar_out.2.bias", 1, s_out, b2)) return false;
         Dense W2(s_out, s_out);
         for (int m = 0; m < s_out; ++m) for (int k = 0; k < s_out; ++k) W2.at(m, k) = w2.at(m, k);
-        o.w2 = pool.add(pack_mfma(W2));
-        o.b2 = pool.add(padded(b2, s_out));
-        o.has_w2 = true;
+        pool.add(pack_mfma(W2), &g.w2);
+        pool.add(padded(b2, s_out), &g.b2);
         std::vector<float> xh, xl;
         pack_x3(W2, xh, xl);
-        o.xw2H = pool.add(xh); o.xw2L = pool.add(xl);
+        pool.add(xh, &x.w2H); pool.add(xl, &x.w2L);
     }
     if (v_out) {
         WView wg, bg, wu;
@@ -450,52 +453,17 @@ bool build_gcp(gcdm_handle* h, Pool& pool, const std::string& pre, int s_in, int
             return false;
         Dense Wg(32, s_out);
         for (int m = 0; m < v_out; ++m) for (int k = 0; k < s_out; ++k) Wg.at(m, k) = wg.at(m, k);
-        o.wg = pool.add(pack_mfma(Wg));
-        o.bg = pool.add(padded(bg, 32));
-        o.wup = pool.add(padded(wu, v_out * H));
-        o.has_gate = true;
+        pool.add(pack_mfma(Wg), &g.wg);
+        pool.add(padded(bg, 32), &g.bg);
+        pool.add(padded(wu, v_out * H), &g.wup);
         if (s_out == 256) {
             std::vector<float> xh, xl;
             pack_gate_x3(Wg, xh, xl);
-            o.xwgH = pool.add(xh); o.xwgL = pool.add(xl);
+            pool.add(xh, &x.wgH); pool.add(xl, &x.wgL);
         }
     }
     return true;
 }
-
-GcpW resolve(const GcpOff& o, const float* base) {
-    GcpW g{};
-    g.w = (const v4f*)(base + o.w);
-    g.b = base + o.b;
-    g.w2 = o.has_w2 ? (const v4f*)(base + o.w2) : nullptr;
-    g.b2 = o.has_w2 ? base + o.b2 : nullptr;
-    g.wdd = base + o.wdd;
-    g.wg = o.has_gate ? (const v4f*)(base + o.wg) : nullptr;
-    g.bg = o.has_gate ? base + o.bg : nullptr;
-    g.wup = o.has_gate ? base + o.wup : nullptr;
-    g.G = o.G; g.H = o.H; g.V_in = o.V_in; g.V_out = o.V_out;
-    return g;
-}
-
-GcpX3 resolve_x3(const GcpOff& o, const float* base) {
-    GcpX3 g{};
-    g.wH = (const h8*)(base + o.xwH); g.wL = (const h8*)(base + o.xwL); g.KB = o.KB;
-    g.w2H = o.has_w2 ? (const h8*)(base + o.xw2H) : nullptr; g.w2L = o.has_w2 ? (const h8*)(base + o.xw2L) : nullptr;
-    g.wgH = o.has_gate ? (const h8*)(base + o.xwgH) : nullptr; g.wgL = o.has_gate ? (const h8*)(base + o.xwgL) : nullptr;
-    g.vmH = o.has_vm ? (const h8*)(base + o.xvmH) : nullptr; g.vmL = o.has_vm ? (const h8*)(base + o.xvmL) : nullptr;
-    return g;
-}
-
-struct LayerOff {
-    size_t w0, wddE, wg0, bg0, wup0, wa, wpq, bpq, wddI, wddJ, bpqx, wax;
-    int G0;
-    float ba;
-    GcpOff mk[3], ff, pos;
-    size_t w0H, w0L, wg0H, wg0L, wH[3], wL[3], wgH[3], wgL[3], wbeH, wbeL;
-    size_t vpH[3], vpL[3], vf1[3], vf2[3], vf0H, vf0L, vdH, vdL;
-    size_t wpqH, wpqL;
-    int KB0, KB;
-};
 
 void free_plan(gcdm_handle* h) {
     if (h->d_noff) (void)hipFree(h->d_noff);
@@ -527,9 +495,270 @@ void free_plan(gcdm_handle* h) {
     h->E = 0;
 }
 
-template <typename K>
-int set_lds_attr(gcdm_handle* h, K kernel, int bytes) {
-    HIP_OK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+// ---- kernel table: which instantiation serves (Se, tile, role), with its launch geometry ---------
+// forward_impl launches through these functions and lds_attr_pass walks them: a kernel that can be launched has its LDS attribute.
+template <class Args>
+struct Kernel { void (*fn)(Args); int threads, lds, tile; };          // block size, dynamic LDS bytes, edges / nodes per workgroup
+
+template <class Args>
+void launch(const Kernel<Args>& k, int grid, hipStream_t st, const Args& a) { hipLaunchKernelGGL(k.fn, dim3(grid), dim3(k.threads), k.lds, st, a); }
+
+Kernel<EdgeEmbedArgs> edge_embed_kernel(int Se) {
+    return Se == 64 ? Kernel<EdgeEmbedArgs>{k_edge_embed<64, 16>, 256, 0, 256} : Kernel<EdgeEmbedArgs>{k_edge_embed<16, 8>, 256, 0, 256};
+}
+Kernel<EdgeEmbedX3Args> edge_embed_x3_kernel(int Se) {          // 4 waves x 32 edges
+    return Se == 64 ? Kernel<EdgeEmbedX3Args>{k_edge_embed_x3<64, 16>, 256, 0, 128} : Kernel<EdgeEmbedX3Args>{k_edge_embed_x3<16, 8>, 256, 0, 128};
+}
+template <int ET>
+Kernel<EdgeMsgArgs> edge_msg_kernel_et(int Se) {
+    return {Se == 64 ? k_edge_msg<64, 16, ET> : k_edge_msg<16, 8, ET>, EdgeGeo<ET>::THREADS, EdgeGeo<ET>::LDS_BYTES, ET};
+}
+Kernel<EdgeMsgArgs> edge_msg_kernel(int Se, int ET) { return ET == 64 ? edge_msg_kernel_et<64>(Se) : edge_msg_kernel_et<32>(Se); }
+
+template <class Role, int ET>
+Kernel<typename Role::Args> edge_x3_kernel_et(int Se) {
+    int lds = EdgeGeo<ET>::LDS_BYTES_X3;
+    if constexpr (Role::ON) lds = Role::LDS_BYTES;
+    return {Se == 64 ? k_edge_msg_x3<64, 16, ET, Role> : k_edge_msg_x3<16, 8, ET, Role>, ET * 8, lds, ET};
+}
+template <class Role>
+Kernel<typename Role::Args> edge_x3_kernel(int Se, int ET) {
+    if constexpr (Role::ON) return edge_x3_kernel_et<Role, 64>(Se);          // the node tail role exists with 64-edge tiles only
+    else return ET == 64 ? edge_x3_kernel_et<Role, 64>(Se) : edge_x3_kernel_et<Role, 32>(Se);
+}
+
+// node stage: the embedding (sc: four input vectors instead of two) or a layer's
+Kernel<NodeArgs> node_kernel(bool embed, bool sc) {
+    return {embed ? (sc ? k_node<true, 4> : k_node<true>) : k_node<false>, 256, NK_LDS_BYTES, NT_};
+}
+Kernel<NodeX3Args> node_x3_kernel(bool embed, bool sc, int node_tile) {
+    if (!embed && node_tile == 64) return {k_node_x3w, 512, NW_LDS_BYTES, NW_T};
+    return {embed ? (sc ? k_node_x3<true, 4> : k_node_x3<true>) : k_node_x3<false>, NX_THREADS, NK_LDS_BYTES, NT_};
+}
+
+template <class Args>
+int set_lds_attr(gcdm_handle* h, const Kernel<Args>& k) {
+    HIP_OK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
+    return 0;
+}
+
+// every kernel of the table that takes dynamic LDS, over the whole (Se, tile, role) set
+int lds_attr_pass(gcdm_handle* h) {
+    for (int Se : {64, 16}) {
+        for (int ET : {64, 32})
+            if (set_lds_attr(h, edge_msg_kernel(Se, ET)) || set_lds_attr(h, edge_x3_kernel<NoTailRole>(Se, ET)) ||
+                set_lds_attr(h, edge_x3_kernel<PackedRole>(Se, ET)))
+                return -1;
+        if (set_lds_attr(h, edge_x3_kernel<NodeTailRole<32>>(Se, 64))) return -1;
+    }
+    for (int embed : {1, 0})
+        for (int sc : {1, 0})
+            if (set_lds_attr(h, node_kernel(embed, sc)) || set_lds_attr(h, node_x3_kernel(embed, sc, 32)) ||
+                set_lds_attr(h, node_x3_kernel(embed, sc, 64)))
+                return -1;
+    return 0;
+}
+
+// ---- one evaluation, stage by stage ---------------------------------------------------------------
+// Tile size of the split-precision layer node kernel.  A 64-node tile streams each weight byte for twice the nodes, but takes ~1.55x the time of a
+// 32-node tile (its load / vector / epilogue phases double, only its GEMM phases do not: 54-71 us against 37-42 us, tests/gpu_node_time.py), and
+// the launch is a whole number of rounds over the CUs: 64-node tiles win where they save a round (GEOM 256 x 44 on one handle: 2 -> 1; a 512-molecule
+// QM9 slice: 2 -> 1), and lose where they do not (QM9 1024 x 19 on one handle: 3 rounds of 32 against 2 of 64).  Same bits either way.
+int node_tile_for(const gcdm_handle* h, int N) {
+    if (h->node_tile) return h->node_tile;
+    const int cus = h->cus > 0 ? h->cus : 256;
+    const int r32 = ((N + 31) / 32 + cus - 1) / cus, r64 = ((N + 63) / 64 + cus - 1) / cus;
+    return 1.55f * r64 < (float)r32 ? 64 : 32;
+}
+
+// The sampler's network evaluations (transition, gcdm_sample_final_sc) feed the time from the step instead of a t [N] tensor and fold the last stage
+// (k_finish) into their k_sample launch: one value for the whole batch, from the device step table when the step is being captured
+struct StepFeed { const StepRow* rows; int* cursor; float t_value; };
+struct Eval {                      // what the stages of one forward share
+    gcdm_handle* h; hipStream_t st; int N, E;
+    int ET, tiles;                 // edges per tile of the layer kernels, tiles of the edge list
+    NodeArgs node;                 // the node stage's arguments that are the same for the embedding and every layer
+};
+
+// profile events of layer l (gcdm_profile_edge_kernel_ms / gcdm_profile_node_kernel_ms): around the edge launch, behind the node stage
+enum LayerEvent { EDGE_BEGIN = 0, EDGE_END = 1, NODE_END = 2 };
+int record_event(const Eval& ev, int l, LayerEvent what) {
+    gcdm_handle* h = ev.h;
+    if (!h->profile) return 0;
+    const size_t i = what == NODE_END ? 2 * (size_t)h->L + l : 2 * (size_t)l + what;
+    HIP_OK(h, hipEventRecord(h->ev[i], ev.st));
+    if (what == EDGE_END) h->ev_used = l + 1;
+    return 0;
+}
+
+void embed_edges(const Eval& ev) {
+    gcdm_handle* h = ev.h;
+    const ModelDev& m = h->m;
+    EdgeEmbedArgs ea{h->X0, h->XC, ev.N, h->d_erow, h->d_ecol, ev.E, m.ee_ws, m.ee_bs, m.ee_wd, m.ee_wdf, m.ee_kappa, m.ee_wg, m.ee_bg,
+                     (v4f*)h->EP4, h->AL, h->U, h->FR,
+                     h->sc, (h->sc ? 2 : 1) + h->Ve + 9, h->X0SC, m.ee_wd1, m.ee_wdf1, m.ee_kappa1, h->BL, h->USC};
+    if (h->use_x3()) {
+        const auto k = edge_embed_x3_kernel(h->Se);
+        launch(k, (ev.E + k.tile - 1) / k.tile, ev.st, EdgeEmbedX3Args{h->x3c(), ea, m.ee_xwH, m.ee_xwL, m.ee_xgH, m.ee_xgL});
+    } else {
+        const auto k = edge_embed_kernel(h->Se);
+        launch(k, (ev.E + k.tile - 1) / k.tile, ev.st, ea);
+    }
+}
+
+// Arguments of the node stage behind layer l (l = -1: the node embedding in front of layer 0): the layer's feed-forward and position update, then the
+// node-level msg0 halves of layer l + 1 or, after the last layer, the output projection.  Layer l gathers set l & 1 of the halves; its node stage writes set (l + 1) & 1.
+NodeArgs node_args(const Eval& ev, int l) {
+    const gcdm_handle* h = ev.h;
+    NodeArgs na = ev.node;
+    const bool setb = ((l + 1) & 1) != 0;
+    na.PQ4 = (v4f*)(setb ? h->PQ4b : h->PQ4); na.VDI = setb ? h->VDIb : h->VDI; na.VDJ = setb ? h->VDJb : h->VDJ;
+    if (l >= 0) {
+        na.agg.tile_shift = ev.ET == 32 ? 5 : 6;
+        na.ff = h->m.layers[l].ff; na.pos = h->m.layers[l].pos;
+    }
+    // (behind the last layer the kernels read none of the msg0 members; they hold the last layer's)
+    const NextMsg0& nm = h->m.layers[std::min(l + 1, h->L - 1)].next;
+    na.has_next = l + 1 < h->L ? 1 : 0;
+    na.wpq = nm.wpq; na.bpq = nm.bpq; na.wddI = nm.wddI; na.wddJ = nm.wddJ;
+    return na;
+}
+
+// ... and the split-precision node kernels' arguments around them
+int node_x3_args(const Eval& ev, int l, NodeX3Args& nx) {
+    gcdm_handle* h = ev.h;
+    nx = NodeX3Args{};
+    nx.x3c = h->x3c();
+    nx.base = node_args(ev, l);
+    nx.emb = h->m.embx; nx.proj = h->m.projx;
+    if (l >= 0) { nx.ff = h->m.layers[l].ffx; nx.pos = h->m.layers[l].posx; }
+    if ((l >= 0 && (nx.ff.KB != 34 || nx.pos.KB != 18)) || nx.proj.KB != 19)      // compile-time k-block counts of k_node_x3
+        return fail(h, "internal: node k-block counts differ from the kernel's compile-time constants");
+    nx.prof = (h->profile_node && l >= 0 && l + 1 < h->L) ? h->PROF : nullptr;
+    const NextMsg0& nm = h->m.layers[std::min(l + 1, h->L - 1)].next;
+    nx.wpqH = nm.wpqH; nx.wpqL = nm.wpqL; nx.vdH = nm.vdH; nx.vdL = nm.vdL; nx.bpqx = nm.bpqx;
+    return 0;
+}
+
+// the node stage as a launch of its own
+int node_stage(const Eval& ev, int l) {
+    gcdm_handle* h = ev.h;
+    const bool embed = l < 0;
+    if (h->use_x3()) {
+        NodeX3Args nx;
+        if (node_x3_args(ev, l, nx)) return -1;
+        const auto k = node_x3_kernel(embed, h->sc, node_tile_for(h, ev.N));
+        launch(k, (ev.N + k.tile - 1) / k.tile, ev.st, nx);
+    } else {
+        const auto k = node_kernel(embed, h->sc);
+        launch(k, (ev.N + k.tile - 1) / k.tile, ev.st, node_args(ev, l));
+    }
+    return 0;
+}
+
+// Layer l's edge-kernel arguments: the template of finalize plus the plan's buffers (the split-precision members are unused by the fp32 kernel, which takes .base)
+EdgeMsgX3Args edge_args(const Eval& ev, int l) {
+    const gcdm_handle* h = ev.h;
+    EdgeMsgX3Args xa = h->m.layers[l].edge;
+    EdgeMsgArgs& ma = xa.base;
+    ma.EP4 = (const v4f*)h->EP4; ma.AL = h->AL; ma.U = h->U; ma.FR = h->FR; ma.EROW = h->d_erow; ma.ECOL = h->d_ecol; ma.NCNT = h->d_ncnt;
+    ma.BL = h->BL; ma.USC = h->USC;
+    const bool odd = (l & 1) != 0;          // the set of node-level msg0 halves this layer gathers
+    ma.E = ev.E; ma.N = ev.N; ma.PQ4 = (const v4f*)(odd ? h->PQ4b : h->PQ4); ma.VDI = odd ? h->VDIb : h->VDI; ma.VDJ = odd ? h->VDJb : h->VDJ; ma.AGG = h->AGG; ma.PART = h->PART;
+    ma.prof = h->profile_phases ? h->PROF : nullptr;
+    ma.TVALID = h->d_tvalid;
+    xa.x3c = h->x3c();
+    xa.wpool = h->wpool; xa.wpool_bytes = (uint32_t)h->wpool_bytes;
+    xa.wspool = h->ws; xa.wspool_bytes = (uint32_t)(h->ws_floats * sizeof(float));
+    xa.flags_dev = h->d_flags;
+    return xa;
+}
+
+int layer_f32(const Eval& ev, int l) {
+    launch(edge_msg_kernel(ev.h->Se, ev.ET), ev.tiles, ev.st, edge_args(ev, l).base);
+    if (record_event(ev, l, EDGE_END)) return -1;
+    return node_stage(ev, l);
+}
+
+// one launch per layer: the node tiles as a tail role of the persistent workgroups (gcdm_layer_x3.hip.h)
+// nodes per node tile of the tail role: 32.  (64-node tiles -- node_tile_x3w -- were built and measured too: QM9 6.85 against 6.94 ms per step on one box,
+// 7.30 against 7.24 on another, GEOM 3.81 against 3.75; their node code keeps one SGPR spilled, which costs the edge role a VGPR: not instantiated)
+int layer_fused(const Eval& ev, int l, const EdgeMsgX3Args& xa, int wgs) {
+    gcdm_handle* h = ev.h;
+    TailArgs ta{};
+    if (node_x3_args(ev, l, ta.nx)) return -1;
+    ta.ready = h->d_tail_ctr; ta.qcur = h->d_tail_ctr + h->tail_tiles32; ta.tab = h->d_tail_tab;
+    ta.num_wgs = wgs;
+    launch(edge_x3_kernel<NodeTailRole<32>>(h->Se, ev.ET), wgs, ev.st, NodeTailRole<32>::Args{xa, ta});
+    return record_event(ev, l, EDGE_END);
+}
+
+// two launches per layer; Role = PackedRole: the same edge kernel with the tiles' real edge counts (gcdm_plan_batches)
+template <class Role>
+int layer_x3_split(const Eval& ev, int l, const EdgeMsgX3Args& xa, int wgs) {
+    launch(edge_x3_kernel<Role>(ev.h->Se, ev.ET), wgs, ev.st, typename Role::Args{xa});
+    if (record_event(ev, l, EDGE_END)) return -1;
+    return node_stage(ev, l);
+}
+
+int layer_x3(const Eval& ev, int l) {
+    gcdm_handle* h = ev.h;
+    EdgeMsgX3Args xa = edge_args(ev, l);
+    if (xa.KB != 18 || xa.KB0 != x3_msg0_kb(h->Se, h->H0)) return fail(h, "internal: k-block counts differ from the kernel's compile-time constants");
+    // persistent workgroups: as many as fit the chip at once (one per CU with 64-edge tiles, two with 32), a multiple of 8 so that every
+    // XCD gets the same number; fewer tiles than that -> one tile per workgroup
+    // (32-edge tiles: 83 KB of LDS, i.e. ONE workgroup per CU -- a grid of 2 x CUs would run in two rounds of one per CU)
+    constexpr int per_cu32 = EdgeGeo<32>::LDS_BYTES_X3 * 2 <= 160 * 1024 ? 2 : 1;
+    int wgs = h->cus * (ev.ET == 64 ? 1 : per_cu32) / 8 * 8;
+    const bool persistent = !(h->persistent == 0 || ev.tiles <= wgs || wgs < 8);
+    if (!persistent) wgs = ev.tiles;
+    xa.wg_stride = persistent ? wgs / 8 : ev.tiles;
+    h->fuse_active = ev.ET == 64 && persistent && h->fuse_node && !h->profile_node && !h->d_mask && h->d_tail_ctr && h->d_tail_tab;
+    if (h->fuse_active) return layer_fused(ev, l, xa, wgs);
+    return h->K ? layer_x3_split<PackedRole>(ev, l, xa, wgs) : layer_x3_split<NoTailRole>(ev, l, xa, wgs);
+}
+
+int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, const float* t, const StepFeed* feed, const float* context, float* out,
+                        uint32_t* flags, void* stream_) {
+    if (!h) return -1;
+    if (xh_sc && !h->sc) return fail(h, "gcdm_forward_sc: the handle was created without self_condition");
+    if (!h->finalized) return fail(h, "gcdm_forward: weights not finalized");
+    if (!h->N) return fail(h, "gcdm_forward: no batch plan");
+    if (!xh || !out) return fail(h, "gcdm_forward: null tensor");
+    if (h->C && !context) return fail(h, "gcdm_forward: context required");
+    DeviceGuard guard(h->cfg.device);
+    Eval ev{};
+    ev.h = h; ev.st = (hipStream_t)stream_; ev.N = h->N; ev.E = (int)h->E;
+    ev.ET = h->tile(); ev.tiles = (ev.E + ev.ET - 1) / ev.ET;
+    const int N = ev.N, B = h->B;
+    h->fuse_active = 0;
+    PrepArgs pa{xh, t, context, h->d_noff, N, h->F, h->C, h->FinG, h->X0, h->XC, h->FBAR, h->CHI0, (v4f*)h->HIN4, h->flat_prev, h->flat_next,
+                h->sc, xh_sc, h->X0SC, h->d_mask};
+    if (feed) { pa.t = nullptr; pa.t_rows = feed->rows; pa.t_cursor = feed->cursor; pa.t_value = feed->t_value; }
+    pa.flags_dev = h->d_flags;            // cleared by the first kernel of the evaluation
+    pa.pack = h->pack();
+    hipLaunchKernelGGL(k_prep, dim3(B), dim3(64), 3 * h->max_n * sizeof(float), ev.st, pa);
+    embed_edges(ev);
+
+    NodeArgs& na = ev.node;
+    na.N = N; na.F = h->F; na.C = h->C; na.FinG = h->FinG; na.Dout = h->D; na.pos_weight = h->cfg.node_positions_weight;
+    na.HIN4 = (const v4f*)h->HIN4; na.CHI0 = h->CHI0; na.emb = h->m.emb;
+    na.agg = AggSrc{h->AGG, h->PART, h->d_rowstart, h->d_ncnt, 0, h->ZROW}; na.H4 = (v4f*)h->H4; na.CHI = h->CHI; na.XC = h->XC; na.X0 = h->X0; na.FBAR = h->FBAR;
+    na.H0 = h->H0;
+    na.proj = h->m.proj; na.OUT = out; na.VEL = h->VEL; na.flags_dev = h->d_flags; na.mask = h->d_mask;
+    if (node_stage(ev, -1)) return -1;          // node embedding; writes set 0 of the msg0 halves for layer 0
+
+    const int L = (h->layer_limit >= 0 && h->layer_limit < h->L) ? h->layer_limit : h->L;
+    for (int l = 0; l < L; ++l) {
+        if (record_event(ev, l, EDGE_BEGIN)) return -1;
+        if (h->use_x3() ? layer_x3(ev, l) : layer_f32(ev, l)) return -1;
+        if (record_event(ev, l, NODE_END)) return -1;          // end of the layer's node kernel (gcdm_profile_node_kernel_ms)
+    }
+    if (L == h->L && !feed) {               // (the sampler's evaluations: inside their k_sample launch)
+        FinishArgs fa{h->VEL, h->d_noff, N, h->D, out, h->d_flags, flags, h->d_mask, h->pack()};
+        hipLaunchKernelGGL(k_finish, dim3(B), dim3(64), 0, ev.st, fa);
+    }
+    HIP_OK(h, hipGetLastError());
     return 0;
 }
 
@@ -616,14 +845,15 @@ int gcdm_set_gamma(gcdm_handle* h, const float* host_gamma, int64_t numel) {
 // One packing pass with the exponent split k (packed weights carry 2^(11-k), X3Const).  Leaves in g_split_absmax the largest magnitude that
 // actually went into an f16 image -- matrices AND what the host folds into them (X3_C factors, the scalar_out biases that ride as the weight
 // column of the constant-1 slot) -- but NOT the parameters that stay fp32 (node-level biases, vector_up tables, ...).
+// The handle changes only at the end, when the new pool is on the device: a pass that fails (a missing or mis-shaped weight) leaves the handle's model and pool as they were.
 static int finalize_pass(gcdm_handle* h, int k_shift) {
     const int S = GCDM_S, V = GCDM_V, Se = h->Se, Ve = h->Ve, H0 = h->H0, L = h->L;
     Pool pool;
+    ModelDev m;
+    m.layers.resize(L);               // (value-initialised; sized before the first add: the pool keeps the addresses of its members)
     g_split_absmax = 0.f;
-    h->x3_shift = k_shift;
     g_split_w = ldexpf(1.0f, 11 - k_shift);
     // ---- edge embedding (1,1) -> (Se,Ve), bottleneck 1: H = max(1, Ve) = Ve ------------------------
-    size_t o_ws, o_bs, o_wd, o_wdf, o_kap, o_wg, o_bg, o_wd1, o_wdf1, o_kap1, o_exwH, o_exwL, o_exgH, o_exgL;
     {
         const std::string p = "gcp_embedding.edge_embedding.";
         WView ws, bs, wd, wdf, wu, wg, bg;
@@ -641,9 +871,9 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
             wd0[c] = wd.at(c, 0); if (h->sc) wd1[c] = wd.at(c, 1);
         }
         for (int k = 0; k < 3; ++k) { wdf0[k] = wdf.at(k, 0); if (h->sc) wdf1[k] = wdf.at(k, 1); }
-        o_ws = pool.add(*ws.v); o_bs = pool.add(*bs.v); o_wd = pool.add(wd0); o_wdf = pool.add(wdf0);
-        o_kap = pool.add(kap); o_wg = pool.add(*wg.v); o_bg = pool.add(*bg.v);
-        o_wd1 = pool.add(wd1); o_wdf1 = pool.add(wdf1); o_kap1 = pool.add(kap1);
+        pool.add(*ws.v, &m.ee_ws); pool.add(*bs.v, &m.ee_bs); pool.add(wd0, &m.ee_wd); pool.add(wdf0, &m.ee_wdf);
+        pool.add(kap, &m.ee_kappa); pool.add(*wg.v, &m.ee_wg); pool.add(*bg.v, &m.ee_bg);
+        pool.add(wd1, &m.ee_wd1); pool.add(wdf1, &m.ee_wdf1); pool.add(kap1, &m.ee_kappa1);
         // split-precision A operands (k_edge_embed_x3, gcdm_embed_x3.hip.h): scalar_out with the K-slot order of that kernel
         // (k = 16 kb + 8 half + s), the bias as the row of the constant-1 slot; vector_out_scale in the register order of the accumulators
         {
@@ -660,7 +890,7 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
             }
             std::vector<float> xh, xl;
             pack_x3(Wp, xh, xl);
-            o_exwH = pool.add(xh); o_exwL = pool.add(xl);
+            pool.add(xh, &m.ee_xwH); pool.add(xl, &m.ee_xwL);
             const int GB = Se / 16;
             std::vector<uint16_t> H((size_t)GB * 64 * 8), Lo(H.size());
             for (int b = 0; b < GB; ++b)
@@ -669,17 +899,17 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
                         const int c = lane & 31, ch = 32 * (b >> 1) + 16 * (b & 1) + 8 * (sl >> 2) + 4 * (lane >> 5) + (sl & 3);
                         split_f16(c < Ve ? wg.at(c, ch) : 0.f, H[((size_t)b * 64 + lane) * 8 + sl], Lo[((size_t)b * 64 + lane) * 8 + sl]);
                     }
-            o_exgH = pool.add(f16_words(H)); o_exgL = pool.add(f16_words(Lo));
+            pool.add(f16_words(H), &m.ee_xgH); pool.add(f16_words(Lo), &m.ee_xgL);
         }
     }
     // ---- node embedding (Fin,2) -> (S,V), bottleneck 1 ------------------------------------------------
-    GcpOff emb, proj;
-    if (!build_gcp(h, pool, "gcp_embedding.node_embedding.", h->Fin, h->sc ? 4 : 2, S, V, 1, false, emb)) return -1;
-    if (!build_gcp(h, pool, "scalar_node_projection_gcp.", S, V, h->FinP, 0, 1, false, proj)) return -1;
-    std::vector<LayerOff> lo(L);
+    if (!build_gcp(h, pool, "gcp_embedding.node_embedding.", h->Fin, h->sc ? 4 : 2, S, V, 1, false, m.emb, m.embx)) return -1;
+    if (!build_gcp(h, pool, "scalar_node_projection_gcp.", S, V, h->FinP, 0, 1, false, m.proj, m.projx)) return -1;
     for (int l = 0; l < L; ++l) {
         const std::string lp = "interaction_layers." + std::to_string(l) + ".";
-        LayerOff& o = lo[l];
+        LayerDev& d = m.layers[l];
+        EdgeMsgX3Args& ex = d.edge;
+        EdgeMsgArgs& ef = ex.base;
         // msg0: scalar_out split into node-level halves (PQ) and the per-edge part [e' | n | q]
         {
             const std::string p = lp + "interaction.message_fusion.0.";
@@ -698,25 +928,25 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
                 for (int k = 0; k < H0; ++k) W0.at(m, 4 * SEG + k) = ws.at(m, 2 * S + Se + k);
                 for (int k = 0; k < 9; ++k) W0.at(m, 4 * (SEG + H0G) + k) = ws.at(m, 2 * S + Se + H0 + k);
             }
-            o.w0 = pool.add(pack_mfma(W0));
-            o.G0 = Kp / 8;
+            pool.add(pack_mfma(W0), &ef.w0);
+            ef.G0 = Kp / 8;
             Dense PQ(2 * S, S);
             for (int m = 0; m < S; ++m)
                 for (int k = 0; k < S; ++k) {
                     PQ.at(m, k) = ws.at(m, k);
                     PQ.at(S + m, k) = ws.at(m, S + Se + k);
                 }
-            o.wpq = pool.add(pack_mfma(PQ));
-            o.bpq = pool.add(padded(bs, 2 * S));
+            pool.add(pack_mfma(PQ), &d.next.wpq);
+            pool.add(padded(bs, 2 * S), &d.next.bpq);
             {   // split-precision path: the node kernel writes c * (P | Q) (scaled units of the edge kernel)
                 Dense PQc(2 * S, S);
                 for (size_t i = 0; i < PQc.a.size(); ++i) PQc.a[i] = PQ.a[i] * X3_C;
                 std::vector<float> xh, xl;
                 pack_x3(PQc, xh, xl);
-                o.wpqH = pool.add(xh); o.wpqL = pool.add(xl);
+                pool.add(xh, &d.next.wpqH); pool.add(xl, &d.next.wpqL);
                 std::vector<float> bc = padded(bs, 2 * S);
                 for (auto& v : bc) v *= X3_C;
-                o.bpqx = pool.add(bc);
+                pool.add(bc, &d.next.bpqx);
             }
             std::vector<float> dI((size_t)(H0 + 3) * V), dJ((size_t)(H0 + 3) * V), dE((size_t)(H0 + 3) * Ve);
             for (int r = 0; r < H0 + 3; ++r) {
@@ -726,27 +956,27 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
                 for (int c = 0; c < Ve; ++c) dE[(size_t)r * Ve + c] = src.at(rr, V + c);
                 for (int c = 0; c < V; ++c) dJ[(size_t)r * V + c] = src.at(rr, V + Ve + c);
             }
-            o.wddI = pool.add(dI); o.wddJ = pool.add(dJ); o.wddE = pool.add(dE);
+            pool.add(dI, &d.next.wddI); pool.add(dJ, &d.next.wddJ); pool.add(dE, &ef.wddE);
             {   // the edge block as ONE split-precision A operand (rows = hidden / frame vectors, padded 32 x 16): beta on the matrix pipe
                 Dense We(32, 16);
                 for (int r = 0; r < H0 + 3; ++r)
                     for (int c = 0; c < Ve; ++c) We.at(r, c) = dE[(size_t)r * Ve + c];
                 std::vector<float> a, b;
                 pack_x3(We, a, b);
-                o.wbeH = pool.add(a); o.wbeL = pool.add(b);
+                pool.add(a, &ex.wbeH); pool.add(b, &ex.wbeL);
             }
             {   // [wddI; wddJ] (2 x (H0 + 3) rows x 32) for the node kernel's matrix-pipe evaluation of VDI / VDJ
                 std::vector<float> dIJ(dI);
                 dIJ.insert(dIJ.end(), dJ.begin(), dJ.end());
                 std::vector<float> a, b;
                 pack_vecmat(dIJ, 2 * (H0 + 3), V, a, b);
-                o.vdH = pool.add(a); o.vdL = pool.add(b);
+                pool.add(a, &d.next.vdH); pool.add(b, &d.next.vdL);
             }
             Dense Wg(32, S);
             for (int m = 0; m < V; ++m) for (int k = 0; k < S; ++k) Wg.at(m, k) = wg.at(m, k);
-            o.wg0 = pool.add(pack_mfma(Wg));
-            o.bg0 = pool.add(padded(bg, 32));
-            o.wup0 = pool.add(*wu.v);
+            pool.add(pack_mfma(Wg), &ef.wg0);
+            pool.add(padded(bg, 32), &ef.bg0);
+            pool.add(*wu.v, &ef.wup0);
             // split-precision images: K' = [e'(Se) | n (H0) | q (9)] compact (round 5), padded to a multiple of 16 (x3_msg0_kb / x3_msg0_qpos)
             const int Kx = 16 * x3_msg0_kb(Se, H0), qpos = x3_msg0_qpos(Se, H0);      // (gcdm_edge_x3.hip.h: the kernel's own layout functions)
             Dense W0x(S, Kx);
@@ -758,19 +988,19 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
             for (auto& v : W0x.a) v *= X3_C;                    // true-unit inputs -> scaled pre-activation
             std::vector<float> xh, xl;
             pack_x3(W0x, xh, xl);
-            o.w0H = pool.add(xh); o.w0L = pool.add(xl); o.KB0 = Kx / 16;
+            pool.add(xh, &ex.w0H); pool.add(xl, &ex.w0L); ex.KB0 = Kx / 16;
             {
                 Dense Wgc(32, S);
                 for (size_t i = 0; i < Wgc.a.size(); ++i) Wgc.a[i] = Wg.a[i] / X3_C;   // acts on the scaled SiLU output
                 pack_gate_x3(Wgc, xh, xl);
             }
-            o.wg0H = pool.add(xh); o.wg0L = pool.add(xl);
+            pool.add(xh, &ex.wg0H); pool.add(xl, &ex.wg0L);
             pack_vec_fin0(wu, H0, xh, xl);
-            o.vf0H = pool.add(xh); o.vf0L = pool.add(xl);
+            pool.add(xh, &ex.vf0H); pool.add(xl, &ex.vf0L);
         }
         for (int k = 1; k <= 3; ++k) {
             const std::string p = lp + "interaction.message_fusion." + std::to_string(k) + ".";
-            if (!build_gcp(h, pool, p, S, V, S, V, 4, false, o.mk[k - 1])) return -1;
+            if (!build_gcp(h, pool, p, S, V, S, V, 4, false, ef.mk[k - 1], d.mkx[k - 1])) return -1;
             // split-precision images: K' = [m.s (256) | n (8) | q (9 -> 16) | pad] = 288
             WView ws, wg, wb;
             if (!get_w(h, p + "scalar_out.weight", S, S + 8 + 9, ws) || !get_w(h, p + "vector_out_scale.weight", V, S, wg) ||
@@ -790,11 +1020,11 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
             }
             std::vector<float> xh, xl;
             pack_x3(Wx, xh, xl);
-            o.wH[k - 1] = pool.add(xh); o.wL[k - 1] = pool.add(xl); o.KB = 18;
+            pool.add(xh, &ex.wH[k - 1]); pool.add(xl, &ex.wL[k - 1]); ex.KB = 18;
             Dense Wgd(32, S);
             for (int m = 0; m < V; ++m) for (int kk = 0; kk < S; ++kk) Wgd.at(m, kk) = wg.at(m, kk) / X3_C;
             pack_gate_x3(Wgd, xh, xl);
-            o.wgH[k - 1] = pool.add(xh); o.wgL[k - 1] = pool.add(xl);
+            pool.add(xh, &ex.wgH[k - 1]); pool.add(xl, &ex.wgL[k - 1]);
             {   // vector path on the matrix pipe: vector_down / vector_down_frames and vector_up as 16x16x32 A operands
                 WView wd, wdf, wu;
                 if (!get_w(h, p + "vector_down.weight", 8, V, wd) || !get_w(h, p + "vector_down_frames.weight", 3, V, wdf) ||
@@ -802,9 +1032,9 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
                     return -1;
                 std::vector<float> a, b;
                 pack_vec_pre(wd, wdf, a, b);
-                o.vpH[k - 1] = pool.add(a); o.vpL[k - 1] = pool.add(b);
+                pool.add(a, &ex.vpH[k - 1]); pool.add(b, &ex.vpL[k - 1]);
                 pack_vec_fin(wu, a, b);
-                o.vf1[k - 1] = pool.add(a); o.vf2[k - 1] = pool.add(b);
+                pool.add(a, &ex.vf1[k - 1]); pool.add(b, &ex.vf2[k - 1]);
             }
         }
         {
@@ -812,68 +1042,32 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
             if (!get_w(h, lp + "interaction.scalar_message_attention.0.weight", 1, S, wa) ||
                 !get_w(h, lp + "interaction.scalar_message_attention.0.bias", 1, 1, ba))
                 return -1;
-            o.wa = pool.add(*wa.v);
-            o.ba = ba.at(0, 0);
+            pool.add(*wa.v, &ef.wa);
+            ef.ba = ba.at(0, 0);
             std::vector<float> wac(*wa.v);
             for (auto& v : wac) v /= X3_C;
-            o.wax = pool.add(wac);
+            pool.add(wac, &ex.wax);
         }
-        if (!build_gcp(h, pool, lp + "feedforward_network.0.", 2 * S, 2 * V, S, V, 4, true, o.ff)) return -1;
-        if (!build_gcp(h, pool, lp + "node_position_update_gcp.", S, V, S, 1, 4, false, o.pos)) return -1;
+        if (!build_gcp(h, pool, lp + "feedforward_network.0.", 2 * S, 2 * V, S, V, 4, true, d.ff, d.ffx)) return -1;
+        if (!build_gcp(h, pool, lp + "node_position_update_gcp.", S, V, S, 1, 4, false, d.pos, d.posx)) return -1;
     }
     pool.host.resize(pool.host.size() + (size_t)X3_TAIL_BLOCKS * 64 * 4 * 2, 0.f);   // un-clamped weight prefetch of the last packed array
-    if (h->wpool) (void)hipFree(h->wpool);
-    h->wpool = nullptr;
-    HIP_OK(h, hipMalloc(&h->wpool, pool.host.size() * sizeof(float)));
-    HIP_OK(h, hipMemcpy(h->wpool, pool.host.data(), pool.host.size() * sizeof(float), hipMemcpyHostToDevice));
-    h->wpool_bytes = pool.host.size() * sizeof(float);
-    if (h->wpool_bytes >= ((size_t)1 << 32)) return fail(h, "gcdm_finalize_weights: weight pool exceeds 4 GB");
-    const float* base = h->wpool;
-    h->ee_ws = base + o_ws; h->ee_bs = base + o_bs; h->ee_wd = base + o_wd; h->ee_wdf = base + o_wdf;
-    h->ee_kappa = base + o_kap; h->ee_wg = base + o_wg; h->ee_bg = base + o_bg;
-    h->ee_wd1 = base + o_wd1; h->ee_wdf1 = base + o_wdf1; h->ee_kappa1 = base + o_kap1;
-    h->ee_xwH = (const h8*)(base + o_exwH); h->ee_xwL = (const h8*)(base + o_exwL); h->ee_xgH = (const h8*)(base + o_exgH); h->ee_xgL = (const h8*)(base + o_exgL);
-    h->emb = resolve(emb, base);
-    h->proj = resolve(proj, base);
-    h->embx = resolve_x3(emb, base);
-    h->projx = resolve_x3(proj, base);
-    h->layers.resize(L);
-    for (int l = 0; l < L; ++l) {
-        const LayerOff& o = lo[l];
-        LayerDev& d = h->layers[l];
-        d.w0 = (const v4f*)(base + o.w0); d.G0 = o.G0; d.wddE = base + o.wddE;
-        d.wg0 = (const v4f*)(base + o.wg0); d.bg0 = base + o.bg0; d.wup0 = base + o.wup0;
-        for (int k = 0; k < 3; ++k) d.mk[k] = resolve(o.mk[k], base);
-        d.wa = base + o.wa; d.ba = o.ba;
-        d.ff = resolve(o.ff, base); d.pos = resolve(o.pos, base);
-        d.wpq = (const v4f*)(base + o.wpq); d.bpq = base + o.bpq; d.wddI = base + o.wddI; d.wddJ = base + o.wddJ;
-        d.w0H = (const h8*)(base + o.w0H); d.w0L = (const h8*)(base + o.w0L); d.KB0 = o.KB0; d.KB = o.KB;
-        d.ffx = resolve_x3(o.ff, base); d.posx = resolve_x3(o.pos, base);
-        d.wpqH = (const h8*)(base + o.wpqH); d.wpqL = (const h8*)(base + o.wpqL);
-        d.wg0H = (const h8*)(base + o.wg0H); d.wg0L = (const h8*)(base + o.wg0L);
-        d.wbeH = (const h8*)(base + o.wbeH); d.wbeL = (const h8*)(base + o.wbeL);
-        d.vf0H = (const h8*)(base + o.vf0H); d.vf0L = (const h8*)(base + o.vf0L);
-        d.vdH = (const h8*)(base + o.vdH); d.vdL = (const h8*)(base + o.vdL);
-        d.bpqx = base + o.bpqx; d.wax = base + o.wax;
-        for (int k = 0; k < 3; ++k) {
-            d.wH[k] = (const h8*)(base + o.wH[k]); d.wL[k] = (const h8*)(base + o.wL[k]);
-            d.wgH[k] = (const h8*)(base + o.wgH[k]); d.wgL[k] = (const h8*)(base + o.wgL[k]);
-            d.vpH[k] = (const h8*)(base + o.vpH[k]); d.vpL[k] = (const h8*)(base + o.vpL[k]);
-            d.vf1[k] = (const h8*)(base + o.vf1[k]); d.vf2[k] = (const h8*)(base + o.vf2[k]);
-        }
+    const size_t bytes = pool.host.size() * sizeof(float);
+    if (bytes >= ((size_t)1 << 32)) return fail(h, "gcdm_finalize_weights: weight pool exceeds 4 GB");
+    float* dev = nullptr;
+    HIP_OK(h, hipMalloc(&dev, bytes));
+    if (hipError_t e = hipMemcpy(dev, pool.host.data(), bytes, hipMemcpyHostToDevice)) {
+        (void)hipFree(dev);
+        return fail(h, std::string("hipMemcpy(weight pool): ") + hipGetErrorString(e));
     }
+    pool.resolve(dev);
+    if (h->wpool) (void)hipFree(h->wpool);
+    h->wpool = dev;
+    h->wpool_bytes = bytes;
+    h->m = std::move(m);              // (the layer vector keeps its storage; the other slots are patched already)
+    h->x3_shift = k_shift;
     if (!h->attr_set) {
-        if (set_lds_attr(h, k_edge_msg<64, 16, 64>, EdgeGeo<64>::LDS_BYTES) || set_lds_attr(h, k_edge_msg<16, 8, 64>, EdgeGeo<64>::LDS_BYTES) ||
-            set_lds_attr(h, k_edge_msg<64, 16, 32>, EdgeGeo<32>::LDS_BYTES) || set_lds_attr(h, k_edge_msg<16, 8, 32>, EdgeGeo<32>::LDS_BYTES) ||
-            set_lds_attr(h, k_edge_msg_x3<64, 16, 64>, EdgeGeo<64>::LDS_BYTES_X3) || set_lds_attr(h, k_edge_msg_x3<16, 8, 64>, EdgeGeo<64>::LDS_BYTES_X3) ||
-            set_lds_attr(h, k_edge_msg_x3<64, 16, 32>, EdgeGeo<32>::LDS_BYTES_X3) || set_lds_attr(h, k_edge_msg_x3<16, 8, 32>, EdgeGeo<32>::LDS_BYTES_X3) ||
-            set_lds_attr(h, k_edge_msg_x3<64, 16, 64, NodeTailRole<32>>, NodeTailRole<32>::LDS_BYTES) || set_lds_attr(h, k_edge_msg_x3<16, 8, 64, NodeTailRole<32>>, NodeTailRole<32>::LDS_BYTES) ||
-            set_lds_attr(h, k_edge_msg_x3<64, 16, 64, PackedRole>, EdgeGeo<64>::LDS_BYTES_X3) || set_lds_attr(h, k_edge_msg_x3<16, 8, 64, PackedRole>, EdgeGeo<64>::LDS_BYTES_X3) ||
-            set_lds_attr(h, k_edge_msg_x3<64, 16, 32, PackedRole>, EdgeGeo<32>::LDS_BYTES_X3) || set_lds_attr(h, k_edge_msg_x3<16, 8, 32, PackedRole>, EdgeGeo<32>::LDS_BYTES_X3) ||
-            set_lds_attr(h, k_node_x3<true>, NK_LDS_BYTES) || set_lds_attr(h, k_node_x3<false>, NK_LDS_BYTES) || set_lds_attr(h, k_node_x3w, NW_LDS_BYTES) ||
-            set_lds_attr(h, k_node<true>, NK_LDS_BYTES) || set_lds_attr(h, k_node<false>, NK_LDS_BYTES) ||
-            set_lds_attr(h, k_node_x3<true, 4>, NK_LDS_BYTES) || set_lds_attr(h, k_node<true, 4>, NK_LDS_BYTES))
-            return -1;
+        if (lds_attr_pass(h)) return -1;
         h->attr_set = true;
     }
     // the packed images hold 2^(11-k) W in f16: if even k = X3_MAX_SHIFT cannot hold the largest packed weight (or one is NaN) -> fp32 MFMA only
@@ -1135,23 +1329,6 @@ int gcdm_debug_set_layer_limit(gcdm_handle* h, int32_t n) {
     return 0;
 }
 
-// Tile size of the split-precision layer node kernel.  A 64-node tile streams each weight byte for twice the nodes, but takes ~1.55x the time of a
-// 32-node tile (its load / vector / epilogue phases double, only its GEMM phases do not: 54-71 us against 37-42 us, tests/gpu_node_time.py), and
-// the launch is a whole number of rounds over the CUs: 64-node tiles win where they save a round (GEOM 256 x 44 on one handle: 2 -> 1; a 512-molecule
-// QM9 slice: 2 -> 1), and lose where they do not (QM9 1024 x 19 on one handle: 3 rounds of 32 against 2 of 64).  Same bits either way.
-static int node_tile_for(const gcdm_handle* h, int N) {
-    if (h->node_tile) return h->node_tile;
-    const int cus = h->cus > 0 ? h->cus : 256;
-    const int r32 = ((N + 31) / 32 + cus - 1) / cus, r64 = ((N + 63) / 64 + cus - 1) / cus;
-    return 1.55f * r64 < (float)r32 ? 64 : 32;
-}
-
-// The sampler's network evaluations (transition, gcdm_sample_final_sc) feed the time from the step instead of a t [N] tensor and fold the last stage
-// (k_finish) into their k_sample launch: one value for the whole batch, from the device step table when the step is being captured
-struct StepFeed { const StepRow* rows; int* cursor; float t_value; };
-static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, const float* t, const StepFeed* feed, const float* context, float* out,
-                        uint32_t* flags, void* stream_);
-
 int gcdm_forward(gcdm_handle* h, const float* xh, const float* t, const float* context, float* out, uint32_t* flags, void* stream_) {
     if (!h) return -1;
     if (!t) return fail(h, "gcdm_forward: null tensor");
@@ -1164,189 +1341,6 @@ int gcdm_forward_sc(gcdm_handle* h, const float* xh, const float* xh_sc, const f
     if (h->K) return refuse_packed(h, "gcdm_forward_sc");
     if (!t) return fail(h, "gcdm_forward: null tensor");
     return forward_impl(h, xh, xh_sc, t, nullptr, context, out, flags, stream_);
-}
-
-static int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, const float* t, const StepFeed* feed, const float* context, float* out,
-                        uint32_t* flags, void* stream_) {
-    if (!h) return -1;
-    if (xh_sc && !h->sc) return fail(h, "gcdm_forward_sc: the handle was created without self_condition");
-    if (!h->finalized) return fail(h, "gcdm_forward: weights not finalized");
-    if (!h->N) return fail(h, "gcdm_forward: no batch plan");
-    if (!xh || !out) return fail(h, "gcdm_forward: null tensor");
-    if (h->C && !context) return fail(h, "gcdm_forward: context required");
-    DeviceGuard guard(h->cfg.device);
-    hipStream_t st = (hipStream_t)stream_;
-    const int N = h->N, B = h->B;
-    const int E = (int)h->E;
-    h->fuse_active = 0;
-    PrepArgs pa{xh, t, context, h->d_noff, N, h->F, h->C, h->FinG, h->X0, h->XC, h->FBAR, h->CHI0, (v4f*)h->HIN4, h->flat_prev, h->flat_next,
-                h->sc, xh_sc, h->X0SC, h->d_mask};
-    if (feed) { pa.t = nullptr; pa.t_rows = feed->rows; pa.t_cursor = feed->cursor; pa.t_value = feed->t_value; }
-    pa.flags_dev = h->d_flags;            // cleared by the first kernel of the evaluation
-    pa.pack = h->pack();
-    hipLaunchKernelGGL(k_prep, dim3(B), dim3(64), 3 * h->max_n * sizeof(float), st, pa);
-    EdgeEmbedArgs ea{h->X0, h->XC, N, h->d_erow, h->d_ecol, E, h->ee_ws, h->ee_bs, h->ee_wd, h->ee_wdf, h->ee_kappa, h->ee_wg, h->ee_bg,
-                     (v4f*)h->EP4, h->AL, h->U, h->FR,
-                     h->sc, (h->sc ? 2 : 1) + h->Ve + 9, h->X0SC, h->ee_wd1, h->ee_wdf1, h->ee_kappa1, h->BL, h->USC};
-    if (h->use_x3()) {
-        EdgeEmbedX3Args ex{h->x3c(), ea, h->ee_xwH, h->ee_xwL, h->ee_xgH, h->ee_xgL};
-        const int egrid = (E + 127) / 128;           // 4 waves x 32 edges
-        if (h->Se == 64) hipLaunchKernelGGL((k_edge_embed_x3<64, 16>), dim3(egrid), dim3(256), 0, st, ex);
-        else hipLaunchKernelGGL((k_edge_embed_x3<16, 8>), dim3(egrid), dim3(256), 0, st, ex);
-    } else {
-        const int egrid = (E + 255) / 256;
-        if (h->Se == 64) hipLaunchKernelGGL((k_edge_embed<64, 16>), dim3(egrid), dim3(256), 0, st, ea);
-        else hipLaunchKernelGGL((k_edge_embed<16, 8>), dim3(egrid), dim3(256), 0, st, ea);
-    }
-
-    const int L = (h->layer_limit >= 0 && h->layer_limit < h->L) ? h->layer_limit : h->L;
-    const bool truncated = L < h->L;
-    NodeArgs na{};
-    na.N = N; na.F = h->F; na.C = h->C; na.FinG = h->FinG; na.Dout = h->D; na.pos_weight = h->cfg.node_positions_weight;
-    na.HIN4 = (const v4f*)h->HIN4; na.CHI0 = h->CHI0; na.emb = h->emb;
-    na.agg = AggSrc{h->AGG, h->PART, h->d_rowstart, h->d_ncnt, 0, h->ZROW}; na.H4 = (v4f*)h->H4; na.CHI = h->CHI; na.XC = h->XC; na.X0 = h->X0; na.FBAR = h->FBAR;
-    na.PQ4 = (v4f*)h->PQ4; na.VDI = h->VDI; na.VDJ = h->VDJ; na.H0 = h->H0;          // (the embedding writes set 0: layer 0 gathers set 0)
-    na.proj = h->proj; na.OUT = out; na.VEL = h->VEL; na.flags_dev = h->d_flags; na.mask = h->d_mask;
-    auto set_next = [&](int l) {
-        if (l < h->L) {
-            const LayerDev& d = h->layers[l];
-            na.has_next = 1; na.wpq = d.wpq; na.bpq = d.bpq; na.wddI = d.wddI; na.wddJ = d.wddJ;
-        } else {
-            na.has_next = 0;
-        }
-    };
-    const int ngrid = (N + NT_ - 1) / NT_;
-    NodeX3Args nx{};
-    nx.x3c = h->x3c();
-    bool node_kb_ok = true;
-    auto prep_node_x3 = [&](int next_layer, const LayerDev* cur) {          // fills nx from na for the split-precision node kernels
-        nx.base = na;
-        nx.emb = h->embx; nx.proj = h->projx;
-        if (cur) { nx.ff = cur->ffx; nx.pos = cur->posx; }
-        if ((cur && (nx.ff.KB != 34 || nx.pos.KB != 18)) || nx.proj.KB != 19) {     // compile-time k-block counts of k_node_x3
-            (void)fail(h, "internal: node k-block counts differ from the kernel's compile-time constants");
-            node_kb_ok = false;
-            return false;
-        }
-        nx.prof = (h->profile_node && cur && next_layer < h->L) ? h->PROF : nullptr;
-        if (next_layer < h->L) { nx.wpqH = h->layers[next_layer].wpqH; nx.wpqL = h->layers[next_layer].wpqL; nx.vdH = h->layers[next_layer].vdH; nx.vdL = h->layers[next_layer].vdL; nx.bpqx = h->layers[next_layer].bpqx; }
-        return true;
-    };
-    auto launch_node = [&](bool embed, int next_layer, const LayerDev* cur) {
-        if (h->use_x3()) {
-            if (!prep_node_x3(next_layer, cur)) return;
-            if (embed && h->sc) hipLaunchKernelGGL((k_node_x3<true, 4>), dim3(ngrid), dim3(NX_THREADS), NK_LDS_BYTES, st, nx);
-            else if (embed) hipLaunchKernelGGL(k_node_x3<true>, dim3(ngrid), dim3(NX_THREADS), NK_LDS_BYTES, st, nx);
-            else if (node_tile_for(h, N) == 64) hipLaunchKernelGGL(k_node_x3w, dim3((N + NW_T - 1) / NW_T), dim3(512), NW_LDS_BYTES, st, nx);
-            else hipLaunchKernelGGL(k_node_x3<false>, dim3(ngrid), dim3(NX_THREADS), NK_LDS_BYTES, st, nx);
-        } else {
-            if (embed && h->sc) hipLaunchKernelGGL((k_node<true, 4>), dim3(ngrid), dim3(256), NK_LDS_BYTES, st, na);
-            else if (embed) hipLaunchKernelGGL(k_node<true>, dim3(ngrid), dim3(256), NK_LDS_BYTES, st, na);
-            else hipLaunchKernelGGL(k_node<false>, dim3(ngrid), dim3(256), NK_LDS_BYTES, st, na);
-        }
-    };
-    set_next(0);
-    launch_node(true, 0, nullptr);
-    if (!node_kb_ok) return -1;
-    const int ET = h->tile();
-    const int tiles = (E + ET - 1) / ET;
-    na.agg.tile_shift = ET == 32 ? 5 : 6;
-    for (int l = 0; l < L; ++l) {
-        const LayerDev& d = h->layers[l];
-        EdgeMsgArgs ma{};
-        ma.EP4 = (const v4f*)h->EP4; ma.AL = h->AL; ma.U = h->U; ma.FR = h->FR; ma.EROW = h->d_erow; ma.ECOL = h->d_ecol; ma.NCNT = h->d_ncnt;
-        ma.BL = h->BL; ma.USC = h->USC;
-        // node-level msg0 halves: layer l gathers set l & 1, its node tiles write set (l + 1) & 1 for layer l + 1
-        const bool odd = (l & 1) != 0;
-        ma.E = E; ma.N = N; ma.PQ4 = (const v4f*)(odd ? h->PQ4b : h->PQ4); ma.VDI = odd ? h->VDIb : h->VDI; ma.VDJ = odd ? h->VDJb : h->VDJ; ma.AGG = h->AGG; ma.PART = h->PART;
-        na.PQ4 = (v4f*)(odd ? h->PQ4 : h->PQ4b); na.VDI = odd ? h->VDI : h->VDIb; na.VDJ = odd ? h->VDJ : h->VDJb;
-        ma.w0 = d.w0; ma.G0 = d.G0; ma.wddE = d.wddE; ma.wg0 = d.wg0; ma.bg0 = d.bg0; ma.wup0 = d.wup0;
-        for (int k = 0; k < 3; ++k) ma.mk[k] = d.mk[k];
-        ma.wa = d.wa; ma.ba = d.ba;
-        ma.prof = h->profile_phases ? h->PROF : nullptr;
-        ma.TVALID = h->d_tvalid;
-        if (h->profile) HIP_OK(h, hipEventRecord(h->ev[2 * l], st));
-        if (h->use_x3()) {
-            EdgeMsgX3Args xa{};
-            xa.x3c = h->x3c();
-            xa.base = ma;
-            xa.w0H = d.w0H; xa.w0L = d.w0L; xa.KB0 = d.KB0; xa.wg0H = d.wg0H; xa.wg0L = d.wg0L; xa.KB = d.KB;
-            xa.wbeH = d.wbeH; xa.wbeL = d.wbeL;
-            for (int k = 0; k < 3; ++k) { xa.wH[k] = d.wH[k]; xa.wL[k] = d.wL[k]; xa.wgH[k] = d.wgH[k]; xa.wgL[k] = d.wgL[k]; }
-            for (int k = 0; k < 3; ++k) { xa.vpH[k] = d.vpH[k]; xa.vpL[k] = d.vpL[k]; xa.vf1[k] = d.vf1[k]; xa.vf2[k] = d.vf2[k]; }
-            xa.vf0H = d.vf0H; xa.vf0L = d.vf0L;
-            xa.wax = d.wax;
-            xa.wpool = h->wpool; xa.wpool_bytes = (uint32_t)h->wpool_bytes;
-            xa.wspool = h->ws; xa.wspool_bytes = (uint32_t)(h->ws_floats * sizeof(float));
-            xa.flags_dev = h->d_flags;
-            if (d.KB != 18 || d.KB0 != x3_msg0_kb(h->Se, h->H0)) return fail(h, "internal: k-block counts differ from the kernel's compile-time constants");
-            // persistent workgroups: as many as fit the chip at once (one per CU with 64-edge tiles, two with 32), a multiple of 8 so that every
-            // XCD gets the same number; fewer tiles than that -> one tile per workgroup, as before
-            // (32-edge tiles: 83 KB of LDS since round 5, i.e. ONE workgroup per CU -- a grid of 2 x CUs would run in two rounds of one per CU)
-            constexpr int per_cu32 = EdgeGeo<32>::LDS_BYTES_X3 * 2 <= 160 * 1024 ? 2 : 1;
-            int wgs = h->cus * (ET == 64 ? 1 : per_cu32) / 8 * 8;
-            bool persistent = true;
-            if (h->persistent == 0 || tiles <= wgs || wgs < 8) { wgs = tiles; xa.wg_stride = tiles; persistent = false; } else xa.wg_stride = wgs / 8;
-            // one launch per layer: the node tiles as a tail role of the persistent workgroups (gcdm_layer_x3.hip.h) where the plan qualifies
-            // nodes per node tile of the tail role: 32.  (64-node tiles -- node_tile_x3w -- were built and measured too: QM9 6.85 against 6.94 ms per step on one box,
-            // 7.30 against 7.24 on another, GEOM 3.81 against 3.75; their node code keeps one SGPR spilled, which costs the edge role a VGPR: not instantiated)
-            h->fuse_active = ET == 64 && persistent && h->fuse_node && !h->profile_node && !h->d_mask && h->d_tail_ctr && h->d_tail_tab;
-            if (h->fuse_active) {
-                na.ff = d.ff; na.pos = d.pos;
-                set_next(l + 1);
-                if (!prep_node_x3(l + 1, &d)) return -1;
-                TailArgs ta{};
-                ta.nx = nx; ta.ready = h->d_tail_ctr; ta.qcur = h->d_tail_ctr + h->tail_tiles32; ta.tab = h->d_tail_tab;
-                ta.num_wgs = wgs;
-                {
-                    NodeTailRole<32>::Args la{xa, ta};
-                    if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 64, NodeTailRole<32>>), dim3(wgs), dim3(512), NodeTailRole<32>::LDS_BYTES, st, la);
-                    else hipLaunchKernelGGL((k_edge_msg_x3<16, 8, 64, NodeTailRole<32>>), dim3(wgs), dim3(512), NodeTailRole<32>::LDS_BYTES, st, la);
-                }
-                if (h->profile) {
-                    HIP_OK(h, hipEventRecord(h->ev[2 * l + 1], st)); h->ev_used = l + 1;
-                    HIP_OK(h, hipEventRecord(h->ev[2 * (size_t)h->L + l], st));
-                }
-                continue;
-            }
-            if (h->K) {             // packed plan: the same kernel with the tiles' real edge counts
-                PackedRole::Args lp{xa};
-                if (ET == 64) {
-                    if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 64, PackedRole>), dim3(wgs), dim3(512), EdgeGeo<64>::LDS_BYTES_X3, st, lp);
-                    else hipLaunchKernelGGL((k_edge_msg_x3<16, 8, 64, PackedRole>), dim3(wgs), dim3(512), EdgeGeo<64>::LDS_BYTES_X3, st, lp);
-                } else {
-                    if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 32, PackedRole>), dim3(wgs), dim3(256), EdgeGeo<32>::LDS_BYTES_X3, st, lp);
-                    else hipLaunchKernelGGL((k_edge_msg_x3<16, 8, 32, PackedRole>), dim3(wgs), dim3(256), EdgeGeo<32>::LDS_BYTES_X3, st, lp);
-                }
-            } else {
-            NoTailRole::Args la{xa};
-            if (ET == 64) {
-                if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 64>), dim3(wgs), dim3(512), EdgeGeo<64>::LDS_BYTES_X3, st, la);
-                else hipLaunchKernelGGL((k_edge_msg_x3<16, 8, 64>), dim3(wgs), dim3(512), EdgeGeo<64>::LDS_BYTES_X3, st, la);
-            } else {
-                if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg_x3<64, 16, 32>), dim3(wgs), dim3(256), EdgeGeo<32>::LDS_BYTES_X3, st, la);
-                else hipLaunchKernelGGL((k_edge_msg_x3<16, 8, 32>), dim3(wgs), dim3(256), EdgeGeo<32>::LDS_BYTES_X3, st, la);
-            }
-            }
-        } else if (ET == 64) {
-            if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg<64, 16, 64>), dim3(tiles), dim3(EdgeGeo<64>::THREADS), EdgeGeo<64>::LDS_BYTES, st, ma);
-            else hipLaunchKernelGGL((k_edge_msg<16, 8, 64>), dim3(tiles), dim3(EdgeGeo<64>::THREADS), EdgeGeo<64>::LDS_BYTES, st, ma);
-        } else {
-            if (h->Se == 64) hipLaunchKernelGGL((k_edge_msg<64, 16, 32>), dim3(tiles), dim3(EdgeGeo<32>::THREADS), EdgeGeo<32>::LDS_BYTES, st, ma);
-            else hipLaunchKernelGGL((k_edge_msg<16, 8, 32>), dim3(tiles), dim3(EdgeGeo<32>::THREADS), EdgeGeo<32>::LDS_BYTES, st, ma);
-        }
-        if (h->profile) { HIP_OK(h, hipEventRecord(h->ev[2 * l + 1], st)); h->ev_used = l + 1; }
-        na.ff = d.ff; na.pos = d.pos;
-        set_next(l + 1);   // next layer's msg0 halves, or the output projection after the last layer
-        launch_node(false, l + 1, &d);
-        if (h->profile) HIP_OK(h, hipEventRecord(h->ev[2 * (size_t)h->L + l], st));      // end of the layer's node kernel (gcdm_profile_node_kernel_ms)
-    }
-    if (!truncated && !feed) {              // (the sampler's evaluations: inside their k_sample launch)
-        FinishArgs fa{h->VEL, h->d_noff, N, h->D, out, h->d_flags, flags, h->d_mask, h->pack()};
-        hipLaunchKernelGGL(k_finish, dim3(B), dim3(64), 0, st, fa);
-    }
-    HIP_OK(h, hipGetLastError());
-    return 0;
 }
 
 // ---- sampler ------------------------------------------------------------------------------------
@@ -1808,10 +1802,10 @@ double gcdm_forward_flops_executed(const gcdm_handle* h) {
     if (!h || !h->N) return 0.0;
     // multiply-adds actually issued per forward (x2; a split-precision product block counts once, padded MFMA rows / columns count), see DESIGN.md section 4
     const double N = h->N, E = (double)h->E, S = GCDM_S, V = GCDM_V, Se = h->Se, Ve = h->Ve, H0 = h->H0;
-    const double G0 = h->layers.empty() ? 0 : h->layers[0].G0;
+    const double G0 = h->m.layers.empty() ? 0 : h->m.layers[0].edge.base.G0;
     const bool x3 = h->use_x3();
     // fp32 kernels: extended-K GEMM + gate + VALU vector products; split-precision kernels: 16-deep k-blocks, vector path on 16x16x32 MFMA tiles
-    const double msg0 = x3 ? 16.0 * (h->layers.empty() ? 0 : h->layers[0].KB0) * S + 32.0 * S + (H0 + 3) * Ve + 3.0 * V * 32
+    const double msg0 = x3 ? 16.0 * (h->m.layers.empty() ? 0 : h->m.layers[0].edge.KB0) * S + 32.0 * S + (H0 + 3) * Ve + 3.0 * V * 32
                            : 8.0 * G0 * S + 32.0 * S + (H0 + 3) * (Ve + 2) * 1.0 + 3.0 * V * H0;
     const double msgk = x3 ? 288.0 * S + 32.0 * S + 16.0 * 32 * 3 + 32.0 * 32 * 3
                            : 280.0 * S + 32.0 * S + 11.0 * 3 * V + 3.0 * V * 8;
@@ -1819,8 +1813,8 @@ double gcdm_forward_flops_executed(const gcdm_handle* h) {
     const double node = 544.0 * S + S * S + 32.0 * S + 19.0 * 3 * 2 * V + 3.0 * V * 16      // ff
                         + 280.0 * S + 32.0 * S + 11.0 * 3 * V + 3.0 * 8                       // pos
                         + 512.0 * S + 2.0 * (H0 + 3) * 3 * V;                                 // next-layer halves
-    const double emb_e = Se * (1 + Ve + 9) + Ve * Se, emb_n = 8.0 * h->emb.G * S + 32.0 * S + 35.0 * 3 * 2 + 3.0 * V * 32;
-    const double proj = 8.0 * h->proj.G * 32 + 35.0 * 3 * V;
+    const double emb_e = Se * (1 + Ve + 9) + Ve * Se, emb_n = 8.0 * h->m.emb.G * S + 32.0 * S + 35.0 * 3 * 2 + 3.0 * V * 32;
+    const double proj = 8.0 * h->m.proj.G * 32 + 35.0 * 3 * V;
     return 2.0 * (h->L * (E * edge + N * node) + E * emb_e + N * (emb_n + proj));
 }
 

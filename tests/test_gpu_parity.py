@@ -935,6 +935,45 @@ def test_cabi_error_paths():
     assert torch.isfinite(z).all()
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_failed_finalize_leaves_the_handle_refusing_and_a_correct_one_restores_the_bits(mode):
+    """gcdm_finalize_weights is transactional: with one weight of the wrong element count it returns < 0 with a message and gcdm_forward is refused;
+    once that weight is sent again correctly it returns 0 and the forward gives the bytes it gave before.  (A successful finalize drops the host
+    copies, so the second upload sends every weight -- one of them wrong; the failed finalize keeps them, so the third sends that one alone.)"""
+    net, W, _ = _net("qm9", seed=3, scale=0.25)
+    dev = torch.device("cuda")
+    net._ensure_handle(dev); net.sync_weights(); net.plan(torch.tensor([4, 5]))
+    net.set_mfma_mode(mode)
+    lib, h = net._lib, net._handle
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda a: C.c_void_p(a.data_ptr())
+    xh, t, _, _, _ = synth.make_inputs([4, 5], synth.dims_feat(_dims("qm9")), seed=2)
+    xh, t = xh.to(dev).contiguous(), t.to(dev).reshape(-1).contiguous()
+
+    def forward():
+        out = torch.full_like(xh, float("nan"))
+        st = lib.gcdm_forward(h, ptr(xh), ptr(t), None, ptr(out), None, stream)
+        torch.cuda.synchronize()
+        return st, out.cpu().numpy().tobytes()
+
+    st, first = forward()
+    assert st == 0 and np.isfinite(np.frombuffer(first, dtype=np.float32)).all()
+    host = {k: v.detach().to(device="cpu", dtype=torch.float32).contiguous() for k, v in net.state_dict().items()}
+    bad = "interaction_layers.4.feedforward_network.0.scalar_out.2.weight"
+    for key, w in host.items():
+        assert lib.gcdm_set_weight(h, key.encode(), ptr(w), w.numel() - (1 if key == bad else 0)) == 0
+    assert lib.gcdm_finalize_weights(h) < 0
+    msg = lib.gcdm_last_error(h)
+    assert msg and b"bad shape" in msg and bad.encode() in msg
+    st, _ = forward()
+    assert st < 0 and b"not finalized" in lib.gcdm_last_error(h)
+    assert lib.gcdm_set_weight(h, bad.encode(), ptr(host[bad]), host[bad].numel()) == 0
+    assert lib.gcdm_finalize_weights(h) == 0
+    assert lib.gcdm_get_option(h, b"mfma_mode") == mode
+    st, again = forward()
+    assert st == 0 and again == first
+
+
 def _raw_noise(seed, N, F):
     """One draw in the reference's randn order: x-part [N,3] then h-part [N,F] (variational_diffusion.py:804-817)."""
     tape = O.TapeNoise(seed)
