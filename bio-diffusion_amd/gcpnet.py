@@ -303,13 +303,16 @@ class GCPNetDynamics(nn.Module):
         ver = self._params_fingerprint()
         if not force and ver == self._weights_version:
             return
-        lib, h = self._lib, self._handle
+        self.upload_weights(self._lib, self._handle)
+        self._weights_version = ver
+
+    def upload_weights(self, lib, h) -> None:
+        """The parameters into handle ``h`` of ``lib`` (the primary handle, or a copy of it on a sampler lane), packed for the kernels."""
         for key, val in self.state_dict().items():
             w = val.detach().to("cpu", torch.float32).contiguous()
             st = lib.gcdm_set_weight(h, key.encode(), C.c_void_p(w.data_ptr()), w.numel())
             _native.check(lib, h, st, f"gcdm_set_weight({key})")
         _native.check(lib, h, lib.gcdm_finalize_weights(h), "gcdm_finalize_weights")
-        self._weights_version = ver
 
     def plan(self, num_nodes, node_mask: Optional[torch.Tensor] = None) -> None:
         """Builds the batch topology (molecule sizes, optionally a node mask with False = masked atoms) once; constant over the sampling loop."""

@@ -1,26 +1,27 @@
-"""Ancestral DDPM sampler around the MI355X dynamics network.
+"""The diffusion model around the MI355X dynamics network: schedule, objective and samplers.
 
-Mirror of the *sampling subset* of ``src/models/components/variational_diffusion.py``:
+Mirror of ``src/models/components/variational_diffusion.py``:
 ``PredefinedNoiseSchedule`` (:206-255), ``EquivariantVariationalDiffusion`` with ``sigma/alpha/SNR`` (:318-338),
 ``sigma_and_alpha_t_given_s`` (:342-367), ``sample_combined_position_feature_noise`` (:795-819),
-``sample_normal`` (:822-837), ``sample_p_zs_given_zt`` (:1204-1278), ``sample_p_xh_given_z0`` (:840-907) and
-``mol_gen_sample`` (:1282-1412), plus ``NumNodesDistribution`` (src/models/__init__.py:264-308).
-RePaint inpainting (``inpaint``, :1582-1789) and the property-guided optimisation loop (``mol_gen_optimize``, :1416-1546) are built
-below on the same step / decode entry points.  ``forward`` (:948-1160) is built for EVALUATION mode -- the validation / test likelihood terms,
-two evaluations of the network per batch; the training objective needs the backward pass of the network and raises.
+``sample_normal`` (:822-837), ``sample_p_zs_given_zt`` (:1204-1278), ``sample_p_xh_given_z0`` (:840-907),
+``mol_gen_sample`` (:1282-1412), RePaint inpainting (``inpaint``, :1582-1789) and the property-guided optimisation loop
+(``mol_gen_optimize``, :1416-1546), plus ``NumNodesDistribution`` (src/models/__init__.py:264-308).
+``forward`` (:948-1160) gives the likelihood terms of a data batch: evaluation mode with two evaluations of the network on the fused kernels,
+training mode with one evaluation under autograd; the algebra around the network runs on HIP operators or (``set_objective_path("fused")``) in
+the fused objective kernels.
 
-Two ways to take a step:
-  * ``sample_p_zs_given_zt`` -- the reference's method signature, torch ops on the device for the O(N) algebra
+Three ways to sample:
+  * ``sample_p_zs_given_zt`` / ``sample_p_xh_given_z0`` -- the reference's method signatures, torch ops on the device for the O(N) algebra
     and the HIP dynamics forward for the network call (used by the teacher-forced parity tests);
-  * ``mol_gen_sample`` -- the production loop: ``gcdm_sample_init / gcdm_sample_step / gcdm_sample_final``
-    (one fused HIP kernel per step after the network kernels; noise from a tape or on-device Philox;
-    host-side asserts replaced by a device flag word read once at the end).
+  * the module-path loops on those methods (masked nodes, position-only diffusion, configurations off the fused sampling kernels);
+  * the production loops on ``gcdm_sample_init / gcdm_sample_step / gcdm_sample_final`` (one fused HIP kernel per step after the network
+    kernels; noise from a tape or on-device Philox; a device flag word read once at the end instead of host-side asserts): their drivers
+    are in ``fused_sampler``; the public methods here check their arguments, choose the loop and call them.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
 import logging
+from itertools import count
 from random import random as _random
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
@@ -29,18 +30,12 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _native, ops
+from . import _native, fused_sampler, ops
 from .config import AttrDict, cfg_get
+from .fused_sampler import RANGE_CHECK_EVERY, _RangeCheckpoints, num_nodes_to_batch_index, slice_cuts  # noqa: F401  (also this module's names)
 from .gcpnet import F16RangeError
 
 log = logging.getLogger(__name__)
-
-
-def num_nodes_to_batch_index(num_samples: int, num_nodes, device) -> torch.Tensor:
-    """src/models/components/__init__.py:314-321."""
-    assert isinstance(num_nodes, int) or len(num_nodes) == num_samples
-    idx = torch.arange(num_samples, device=device)
-    return torch.repeat_interleave(idx, num_nodes if isinstance(num_nodes, int) else num_nodes.to(device))
 
 
 def inflate_batch_array(array: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -77,24 +72,6 @@ def cosine_gamma(num_timesteps: int, s: float = 0.008) -> np.ndarray:
     return -(np.log(a2) - np.log(1 - a2))
 
 
-def slice_cuts(num_nodes: torch.Tensor, K: int) -> List[int]:
-    """Molecule indices [c_0 = 0, c_1, ..., c_K = B] that cut a flat batch into K contiguous, non-empty slices of roughly equal work
-    (edges, i.e. sum of n^2) -- used when one batch is sampled on K handles / streams."""
-    nn_ = torch.as_tensor(num_nodes).long().cpu()
-    Bm = len(nn_)
-    if not 1 <= K <= Bm:
-        raise ValueError(f"cannot cut {Bm} molecules into {K} non-empty slices")
-    work_cum = (nn_ ** 2).cumsum(0)
-    cuts = [0]
-    # (round 5 measured unequal cuts -- the first slice's tile count a multiple of the persistent workgroup count, 0.4873 / 0.5127 / 0.45 / 0.531 of the work:
-    #  6.93 / 6.92 / 6.95 / 6.85 ms per step against 6.88 for the equal cut, profiles/r05_slices.txt: the dispatcher already fills one slice's tails with the other)
-    for k in range(1, K):
-        c = int(torch.searchsorted(work_cum, work_cum[-1] * k // K).item()) + 1
-        cuts.append(min(max(c, cuts[-1] + 1), Bm - (K - k)))
-    cuts.append(Bm)
-    return cuts
-
-
 def repaint_schedule(resamplings: int, jump_length: int, num_timesteps: int) -> List[int]:
     """RePaint schedule (variational_diffusion.py:1548-1578, `get_repaint_schedule`): the number of denoising steps to apply before each
     jump back, from t = T downwards.  T is cut into ``(T-1) // jump_length`` stretches of ``jump_length`` steps plus a remainder; every
@@ -114,6 +91,22 @@ def repaint_schedule(resamplings: int, jump_length: int, num_timesteps: int) -> 
     low_to_high += ([2 * jump_length] + [jump_length] * (resamplings - 2)) * (stretches - 1)
     low_to_high.append(jump_length + rest)
     return low_to_high[::-1]
+
+
+def _check_frames(return_frames: int, num_timesteps: int) -> None:
+    assert 0 < return_frames <= num_timesteps, "Number of frames cannot be greater than number of timesteps."
+    assert num_timesteps % return_frames == 0, "Number of frames must be evenly divisible by number of timesteps."
+
+
+def _module_draws(noise_fn: Optional[Callable[[int], torch.Tensor]], seed: int, device) -> Tuple[Optional[torch.Generator], Callable[[], Optional[torch.Tensor]]]:
+    """Noise of a module-path loop, as (generator, draw): ``draw()`` is the next raw draw of the tape (k = 0, 1, ...), or None without a tape -- the
+    draws then come from the device generator seeded with ``seed``, so that a re-run after F16RangeError draws the same noise."""
+    if noise_fn is None:
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(seed))
+        return gen, lambda: None
+    k = count()
+    return None, lambda: noise_fn(next(k)).to(device, torch.float32)
 
 
 class PredefinedNoiseSchedule(nn.Module):
@@ -159,129 +152,6 @@ class NumNodesDistribution(nn.Module):
     def log_prob(self, batch_n_nodes: torch.Tensor) -> torch.Tensor:
         idcs = torch.tensor([self.keys[n] for n in batch_n_nodes.tolist()], device=batch_n_nodes.device)        # one host copy, not one per molecule
         return torch.log(self.prob + self.eps)[idcs]
-
-
-RANGE_CHECK_EVERY = 25          # steps between two looks at the f16-range flag inside the fused sampling loops
-
-
-def _pinned_flag_copy(flags: torch.Tensor) -> Callable[[], List[int]]:
-    """Asynchronous copy of the device flag word(s) to pinned host memory, on the current stream; returns the reader that waits for it."""
-    host = torch.zeros(flags.numel(), dtype=torch.int32).pin_memory()
-    host.copy_(flags, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(flags.device))
-
-    def read() -> List[int]:
-        ev.synchronize()
-        return [int(v) for v in host.tolist()]
-    return read
-
-
-class _RangeCheckpoints:
-    """Range guard of the split-precision mode INSIDE a sampling loop, and the loop itself (``run``).  Every RANGE_CHECK_EVERY steps the loop
-    hands over a snapshot of its state (latent + counters) together with an asynchronous copy of the device flag word; one interval later
-    that copy has long arrived and is looked at without stalling the GPU: clean -> the snapshot becomes the restart point;
-    GCDM_FLAG_F16_RANGE -> the loop resumes from the previous restart point with fp32 MFMA instead of re-running the whole trajectory (an
-    overflow at step 900 of 1000 costs <= 1.3x a clean run; it used to cost 1 + 2.7).  ``active=False`` (the handle already runs fp32 MFMA):
-    the plain loop.  ``copy_flags(flags)`` starts the flag copy and returns its reader (default: pinned copy + event)."""
-
-    def __init__(self, active: bool = True, copy_flags: Callable[[torch.Tensor], Callable[[], List[int]]] = _pinned_flag_copy):
-        self.active = active
-        self.copy_flags = copy_flags
-        self.good = None             # (state, tensors) verified clean
-        self.pend = None             # (state, tensors, reader of the flag copy) waiting for its flag copy
-        self.rewinds = 0
-        self.fell_back = False       # the handle was switched to fp32 MFMA at step resume_step
-        self.resume_step = None
-        self.tail_flag = False       # GCDM_FLAG_TAIL in any flag word looked at (the caller disables the fused layer launch)
-
-    def run(self, num_timesteps: int, step: Callable[[int], None], final: Callable[[], int], flags: torch.Tensor,
-            save: Callable[[], Tuple[Dict[str, Any], List[torch.Tensor]]], load: Callable[[Dict[str, Any], List[torch.Tensor]], None],
-            set_mode: Callable[[int], None], wait: Callable[[], None] = lambda: None, fence: Callable[[], None] = lambda: None) -> int:
-        """Steps s = num_timesteps - 1 ... 0, then the final decode; returns its flag word (the caller reports it).  ``step(s)`` / ``final()``
-        enqueue the work (``final`` reads the flag word: the one host sync of a clean run); ``save()`` -> (counters, latent tensors) and
-        ``load(counters, copies)`` put a snapshot back; ``set_mode(m)`` switches the handle(s) between fp32 (0) and split-precision (1) MFMA;
-        ``wait()`` / ``fence()`` order the caller's stream after / before the work around a snapshot or restore (several streams)."""
-        def restart(point):
-            st, copies = point
-            wait()
-            load(st, copies)
-            self.restore_flags(flags, st)
-            if not self.fell_back:
-                log.warning("An activation left the f16 range of the split-precision kernels; resuming from step %d with fp32 MFMA.", st["s"])
-                set_mode(0)
-                self.fell_back, self.resume_step = True, st["s"]
-            fence()
-            return st["s"]
-
-        try:
-            s = num_timesteps - 1
-            if self.active:
-                wait()
-                st, tensors = save()
-                self.good = (dict(st, s=s), [t.clone() for t in tensors])
-                fence()
-            while True:
-                while s >= 0:
-                    if self.active and not self.fell_back and (num_timesteps - 1 - s) % RANGE_CHECK_EVERY == 0 and s != num_timesteps - 1:
-                        wait()
-                        st, tensors = save()
-                        point = self.snapshot(dict(st, s=s), tensors, flags)
-                        fence()
-                        if point is not None:
-                            s = restart(point)
-                            continue
-                    step(s)
-                    s -= 1
-                fl = final()
-                point = self.resolve(fl) if (self.active and not self.fell_back) else None
-                if point is None:
-                    return fl
-                s = restart(point)       # an overflow in the last interval (or in the decode): repeat it in fp32
-        finally:
-            if self.fell_back:
-                set_mode(1)
-
-    def snapshot(self, state: Dict[str, Any], tensors: List[torch.Tensor], flags: torch.Tensor):
-        """Called on the stream the latent is valid on.  Returns the restart point to rewind to if the PREVIOUS snapshot's flag is dirty."""
-        rewind = self.resolve()
-        if rewind is not None:
-            return rewind
-        copies = [t.clone() for t in tensors]
-        self.pend = (dict(state), copies, self.copy_flags(flags))
-        return None
-
-    def resolve(self, final_flags: Optional[int] = None):
-        """Looks at the pending snapshot's flag copy (or, at the end of the run, at the final flag word).  Returns (state, tensors) to rewind
-        to, or None if the trajectory so far is clean."""
-        if self.pend is not None:
-            st, copies, read = self.pend
-            host = read()
-            self.pend = None
-            self.tail_flag |= any(v & _native.FLAG_TAIL for v in host)
-            if any(v & _native.FLAG_F16_RANGE for v in host):
-                return self._rewind()
-            st["flags"] = host                                 # the flag word(s) AT the snapshot: what a rewind restores (bits raised during a
-            self.good = (st, copies)                           # discarded f16 interval -- NaN in vel, CoG drift -- must not survive it)
-        if final_flags is not None:
-            self.tail_flag |= bool(final_flags & _native.FLAG_TAIL)
-            if final_flags & _native.FLAG_F16_RANGE:
-                return self._rewind()
-        return None
-
-    def _rewind(self):
-        self.rewinds += 1
-        return self.good
-
-    @staticmethod
-    def restore_flags(flags: torch.Tensor, state: Dict[str, Any]) -> None:
-        """Device flag word(s) back to their value at the restart point.  The first restart point (start of the loop) has no copy: only the
-        bits a network evaluation / decode can raise are cleared there (a mean-not-zero flag of the encode step in front of it stays)."""
-        saved = state.get("flags")
-        if saved is not None:
-            flags.copy_(torch.tensor(saved, dtype=flags.dtype).to(flags.device, non_blocking=True))
-        else:
-            flags.bitwise_and_(~(_native.FLAG_F16_RANGE | _native.FLAG_NAN_VEL | _native.FLAG_COG_DRIFT | _native.FLAG_TAIL))
 
 
 class _Batch(AttrDict):
@@ -782,8 +652,7 @@ class EquivariantVariationalDiffusion(nn.Module):
         dyn.sync_weights()
         lib, h = dyn._lib, dyn._handle
         if self._gamma_uploaded is not h:
-            g = self.gamma.gamma.detach().to("cpu", torch.float32).contiguous()
-            _native.check(lib, h, lib.gcdm_set_gamma(h, C.c_void_p(g.data_ptr()), g.numel()), "gcdm_set_gamma")
+            fused_sampler.upload_gamma(self, lib, h)
             self._gamma_uploaded = h
         return dyn, lib, h
 
@@ -795,38 +664,22 @@ class EquivariantVariationalDiffusion(nn.Module):
         without it the draws come from a device torch.Generator seeded with ``seed`` (reproducible per seed, in the reference's randn order,
         so that a re-run after F16RangeError draws the same noise)."""
         num_timesteps = self.T if num_timesteps is None else num_timesteps
-        assert 0 < return_frames <= num_timesteps, "Number of frames cannot be greater than number of timesteps."
-        assert num_timesteps % return_frames == 0, "Number of frames must be evenly divisible by number of timesteps."
+        _check_frames(return_frames, num_timesteps)
         num_nodes = torch.as_tensor(num_nodes)
         bi = num_nodes_to_batch_index(num_samples, num_nodes.to(device), device=device)
         node_mask = torch.ones_like(bi).bool() if node_mask is None else node_mask.to(device)
         if context is not None:
             context = context.to(device)[bi] * node_mask.float().unsqueeze(-1)
         t_norm = self.T if norm_with_original_timesteps else num_timesteps
-        k = [0]
-        gen = None
-        if noise_fn is None:
-            gen = torch.Generator(device=device)
-            gen.manual_seed(int(seed))
-
-        def draw():
-            if noise_fn is None:
-                return None
-            k[0] += 1
-            return noise_fn(k[0] - 1).to(device, torch.float32)
-
+        gen, draw = _module_draws(noise_fn, seed, device)
         m = node_mask.float().unsqueeze(-1)
-        raw = None
+        raw = draw() if init_xh is None else None
         if init_xh is not None:
             # optimisation loop (mol_gen_optimize :1451-1464): z = normalize(samples), no initial draw; the reference's assert_mean_zero_with_mask
             xin = init_xh.to(device, torch.float32)
             nv, nb = cfg_get(self.diffusion_cfg, "norm_values"), cfg_get(self.diffusion_cfg, "norm_biases")
             z = torch.cat((xin[:, : self.num_x_dims] / nv[0], (xin[:, self.num_x_dims:] - nb[1]) / nv[1] * m), dim=-1)
             self.assert_mean_zero_with_mask(z[:, : self.num_x_dims], node_mask)
-        else:
-            raw = draw()
-        if init_xh is not None:
-            pass
         elif raw is None:
             z = self.sample_combined_position_feature_noise(torch.zeros_like(bi) if fix_noise else bi, node_mask, generate_x_only=generate_x_only,
                                                             generator=gen, num_graphs=1 if fix_noise else num_samples)
@@ -850,13 +703,20 @@ class EquivariantVariationalDiffusion(nn.Module):
         x, h = self.sample_p_xh_given_z0(z_0=z, batch_index=bi, node_mask=node_mask, batch_size=num_samples, context=context,
                                          fix_noise=fix_self_conditioning_noise if self_cond_on else fix_noise, generate_x_only=generate_x_only,
                                          xh_self_cond=self_cond, noise=draw(), generator=gen)
-        if return_frames == 1:
-            cog = torch.zeros(num_samples, self.num_x_dims, device=device).index_add_(0, bi, x).abs().max().item()
-            if cog > 5e-2:
-                x = _segment_mean_sub(x, bi, num_samples, node_mask)
-        out[0] = x if generate_x_only else torch.cat([x, h["categorical"].to(x.dtype)] + ([h["integer"].to(x.dtype)] if self.include_charges else []), dim=-1)
+        out[0] = self._decoded_frame(x, h, bi, num_samples, node_mask, return_frames, generate_x_only)
         self.last_flags = 0
         return out.squeeze(0), bi, node_mask
+
+    def _decoded_frame(self, x, h, bi, num_graphs, node_mask, return_frames, generate_x_only):
+        """Frame 0 of a module-path loop from the decode's (x, h): the positions re-centred where the centres of gravity drifted (runs without
+        intermediate frames only, :1389-1402), then [x, one-hot, charges]."""
+        if return_frames == 1:
+            cog = torch.zeros(num_graphs, self.num_x_dims, device=x.device).index_add_(0, bi, x).abs().max().item()
+            if cog > 5e-2:
+                x = _segment_mean_sub(x, bi, num_graphs, node_mask)
+        if generate_x_only:
+            return x
+        return torch.cat([x, h["categorical"].to(x.dtype)] + ([h["integer"].to(x.dtype)] if self.include_charges else []), dim=-1)
 
     def unnormalize_z(self, z, node_mask, generate_x_only: bool = False):
         """(:761-793)"""
@@ -878,14 +738,8 @@ class EquivariantVariationalDiffusion(nn.Module):
         """Draw samples.  ``noise_fn(k)`` (optional) returns the k-th raw standard-normal draw [N,3+F] on ``device``
         (k = 0 for z_T, then one per step, then one for the final decode: the reference's randn call order,
         SURVEY A.5); without it noise comes from on-device Philox(seed)."""
-        # position-only diffusion (:1292, 1325-1327, 1349, 1385, 1407-1408): z = z_x, every draw is the centred x-noise alone, the result is the
-        # [N, 3] positions.  It needs a dynamics network built WITHOUT node features (dataloader_cfg.num_atom_types = 0, include_charges = False:
-        # xh is [N, 3] then, as in the reference) -- the general loop on the module path.
-        if generate_x_only and getattr(self.dynamics_network, "num_atom_types", 0) + int(getattr(self.dynamics_network, "include_charges", False)) > 0:
-            raise ValueError("generate_x_only needs a dynamics network built without node features (num_atom_types = 0, include_charges = False); "
-                             "the reference fails on the feature width of this one too (gcpnet.py:1093-1110)")
-        if (generate_x_only or (node_mask is not None and not bool(node_mask.all()))
-                or getattr(self.dynamics_network, "fused_unsupported", None) is not None or getattr(self.dynamics_network, "path", "auto") == "modules"):
+        self._check_x_only_network(generate_x_only)
+        if self._off_fused_kernels(generate_x_only, node_mask):
             # general loop: position-only diffusion, masked nodes inside the loop, or a configuration the fused sampling kernels are not built for
             if _t_norm is not None:
                 raise NotImplementedError("an explicit time normalisation runs on the fused path only")
@@ -900,8 +754,7 @@ class EquivariantVariationalDiffusion(nn.Module):
         if self_cond_on and fix_self_conditioning_noise != fix_noise:
             raise NotImplementedError("fix_self_conditioning_noise must equal fix_noise")
         num_timesteps = self.T if num_timesteps is None else num_timesteps
-        assert 0 < return_frames <= num_timesteps, "Number of frames cannot be greater than number of timesteps."
-        assert num_timesteps % return_frames == 0, "Number of frames must be evenly divisible by number of timesteps."
+        _check_frames(return_frames, num_timesteps)
         # time normalisation of the loop (:1333-1341): s / T_norm with T_norm = self.T if norm_with_original_timesteps else num_timesteps
         t_norm = _t_norm if _t_norm is not None else (self.T if norm_with_original_timesteps else num_timesteps)
         if num_timesteps > t_norm:
@@ -909,91 +762,23 @@ class EquivariantVariationalDiffusion(nn.Module):
         if lanes > 1 and len(num_nodes) >= 2 * lanes and not (
                 noise_fn is not None or return_frames != 1 or _init_xh is not None or step_callback is not None):
             # slices of the flat batch on several handles / streams: plain sampling with on-device noise; anything else runs on one handle
-            return self._mol_gen_sample_lanes(num_samples, num_nodes, device, num_timesteps, t_norm, context, seed, lanes)
-        device = torch.device(device)
-        dyn, lib, h = self._native(device)
-        num_nodes = torch.as_tensor(num_nodes)
-        batch_index = num_nodes_to_batch_index(num_samples, num_nodes.to(device), device=device)
-        node_mask = torch.ones_like(batch_index).bool()
-        dyn.plan(num_nodes.cpu())
-        N, D = int(batch_index.shape[0]), self.num_x_dims + self.num_node_scalar_features
-        ctx_ptr = None
-        context_in = context
-        if context is not None:
-            context = context.to(device, torch.float32)[batch_index].contiguous()
-            ctx_ptr = C.c_void_p(context.data_ptr())
-        elif dyn.condition_on_context:
-            raise ValueError("context required by a context-conditioned model")
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        flags = torch.zeros(1, dtype=torch.int32, device=device)
-        fptr = C.c_void_p(flags.data_ptr())
-        z = torch.empty((N, D), dtype=torch.float32, device=device)
-        _native.check(lib, h, lib.gcdm_set_option(h, b"fix_noise", int(bool(fix_noise))), "gcdm_set_option")
-        frames = torch.zeros((return_frames, N, D), dtype=torch.float32, device=device)     # frame 0 = the final sample (:1404-1410)
-        out = frames[0]
-        k = 0
+            return fused_sampler.sample_lanes(self, num_nodes, torch.device(device), num_timesteps, t_norm, context, seed, lanes)
+        assert len(num_nodes) == num_samples
+        return fused_sampler.sample(self, num_nodes, torch.device(device), return_frames, num_timesteps, t_norm, context, fix_noise, noise_fn, seed,
+                                    step_callback, _init_xh)
 
-        def nptr():
-            nonlocal k
-            if noise_fn is None:
-                k += 1
-                return None, None
-            nz = noise_fn(k).to(device, torch.float32).contiguous()
-            k += 1
-            return nz, C.c_void_p(nz.data_ptr())
+    def _check_x_only_network(self, generate_x_only: bool) -> None:
+        """Position-only diffusion (:1292, 1325-1327, 1349, 1385, 1407-1408: z = z_x, centred x-noise alone, [N, 3] out) needs a dynamics network
+        built WITHOUT node features (dataloader_cfg.num_atom_types = 0, include_charges = False: xh is [N, 3] then, as in the reference)."""
+        if generate_x_only and getattr(self.dynamics_network, "num_atom_types", 0) + int(getattr(self.dynamics_network, "include_charges", False)) > 0:
+            raise ValueError("generate_x_only needs a dynamics network built without node features (num_atom_types = 0, include_charges = False); "
+                             "the reference fails on the feature width of this one too (gcpnet.py:1093-1110)")
 
-        if _init_xh is None:
-            keep, p = nptr()
-            _native.check(lib, h, lib.gcdm_sample_init(h, C.c_void_p(z.data_ptr()), p, C.c_uint64(seed), stream), "gcdm_sample_init")
-        else:                                # optimisation loop: z = normalize(samples) (:1451-1464), no initial draw
-            xin = _init_xh.to(device, torch.float32).contiguous()
-            if xin.shape != (N, D):
-                raise ValueError(f"samples have shape {tuple(xin.shape)}, expected {(N, D)}")
-            _native.check(lib, h, lib.gcdm_encode_samples(h, C.c_void_p(xin.data_ptr()), C.c_void_p(z.data_ptr()), fptr, stream),
-                          "gcdm_encode_samples")
-        self_cond = torch.zeros_like(z) if self_cond_on else None     # the estimate fed back into the next step (:1363-1375)
-        latent = [z] + ([self_cond] if self_cond_on else [])
-
-        def step(s):
-            keep, p = nptr()
-            if self_cond_on:
-                keep2, p2 = nptr()
-                st = lib.gcdm_sample_step_sc(h, C.c_void_p(z.data_ptr()), C.c_void_p(self_cond.data_ptr()), int(s != num_timesteps - 1), ctx_ptr, s, t_norm,
-                                             p, p2, C.c_uint64(seed), fptr, stream)
-            else:
-                st = lib.gcdm_sample_step(h, C.c_void_p(z.data_ptr()), ctx_ptr, s, t_norm, p, C.c_uint64(seed), fptr, stream)
-            _native.check(lib, h, st, "gcdm_sample_step")
-            if return_frames > 1 and (s * return_frames) % num_timesteps == 0:             # save frame (:1354-1361)
-                fr = frames[(s * return_frames) // num_timesteps]
-                _native.check(lib, h, lib.gcdm_unnormalize_z(h, C.c_void_p(z.data_ptr()), C.c_void_p(fr.data_ptr()), stream), "gcdm_unnormalize_z")
-            if step_callback is not None:
-                step_callback(s, z)              # (fires again for the steps a resumed run repeats)
-
-        def final():
-            keep, p = nptr()
-            _native.check(lib, h, lib.gcdm_set_option(h, b"cog_fix", 1 if return_frames == 1 else 0), "gcdm_set_option")   # :1389
-            if self_cond_on:
-                st = lib.gcdm_sample_final_sc(h, C.c_void_p(z.data_ptr()), C.c_void_p(self_cond.data_ptr()) if num_timesteps > 0 else None, ctx_ptr, p,
-                                              C.c_uint64(seed), C.c_void_p(out.data_ptr()), fptr, stream)
-            else:
-                st = lib.gcdm_sample_final(h, C.c_void_p(z.data_ptr()), ctx_ptr, p, C.c_uint64(seed), C.c_void_p(out.data_ptr()), fptr, stream)
-            lib.gcdm_set_option(h, b"cog_fix", 1)
-            _native.check(lib, h, st, "gcdm_sample_final")
-            return int(flags.item())             # the one host sync of a clean run
-
-        def load(st, copies):
-            nonlocal k
-            for t_, c_ in zip(latent, copies):
-                t_.copy_(c_)
-            k = st["k"]
-
-        guard = _RangeCheckpoints(active=dyn.mfma_mode == 1)
-        try:
-            fl = guard.run(num_timesteps, step, final, flags, lambda: ({"k": k}, latent), load, dyn.set_mfma_mode)
-        finally:
-            lib.gcdm_set_option(h, b"fix_noise", 0)
-        self._report_flags(fl, "mol_gen_sample", guard)
-        return (out if return_frames == 1 else frames), batch_index, node_mask
+    def _off_fused_kernels(self, generate_x_only: bool, node_mask: Optional[torch.Tensor] = None) -> bool:
+        """Does this call run the general loop on the module path (position-only diffusion, masked nodes inside the loop, a configuration the
+        fused sampling kernels are not built for, ``dynamics_network.path = "modules"``) instead of the fused kernels?"""
+        return bool(generate_x_only or (node_mask is not None and not bool(node_mask.all()))
+                    or getattr(self.dynamics_network, "fused_unsupported", None) is not None or getattr(self.dynamics_network, "path", "auto") == "modules")
 
     @torch.inference_mode()
     def inpaint(self, molecule: Dict[str, Any], node_mask_fixed: torch.Tensor, num_resamplings: int = 1, jump_length: int = 1,
@@ -1006,99 +791,17 @@ class EquivariantVariationalDiffusion(nn.Module):
         DESIGN.md 7), pinned by tests/golden/inpaint_small_qm9.npz.  ``noise_fn(k)``: the k-th raw draw in the reference's order -- z_T, then
         per step [known part, model step, self-conditioning estimate if any], one per jump back, and the final decode."""
         num_timesteps = self.T if num_timesteps is None else num_timesteps
-        assert 0 < return_frames <= num_timesteps, "Number of frames cannot be greater than number of timesteps."
-        assert num_timesteps % return_frames == 0, "Number of frames must be evenly divisible by number of timesteps."
+        _check_frames(return_frames, num_timesteps)
         assert jump_length == 1 or return_frames == 1, "Chain visualization is only implemented for `jump_length=1`"
-        if (generate_x_only or getattr(self.dynamics_network, "fused_unsupported", None) is not None
-                or getattr(self.dynamics_network, "path", "auto") == "modules"):
+        if self._off_fused_kernels(generate_x_only):
             # position-only diffusion (a dynamics network without node features) and configurations off the fused kernels: the general loop
             return self._rerun_in_fp32(lambda: self._inpaint_modules(molecule, node_mask_fixed, num_resamplings, jump_length, return_frames,
                                                                      num_timesteps, context, generate_x_only, noise_fn, seed),
                                        "the inpainting loop")
-        return self._rerun_in_fp32(lambda: self._inpaint_fused_once(molecule, node_mask_fixed, num_resamplings, jump_length, return_frames,
-                                                                    num_timesteps, context, noise_fn, seed),
-                                   "the inpainting")
-
-    def _inpaint_fused_once(self, molecule, node_mask_fixed, num_resamplings, jump_length, return_frames, num_timesteps, context, noise_fn, seed):
-        """inpaint on the fused kernels, one run.  Raises F16RangeError if an activation left the f16 range of the split-precision kernels."""
-        num_nodes = torch.as_tensor(molecule["num_nodes"])
-        device = torch.device(molecule["x"].device)
-        dyn, lib, h = self._native(device)
-        self_cond_on = bool(getattr(dyn, "self_condition", False))
-        batch_index = num_nodes_to_batch_index(len(num_nodes), num_nodes.to(device), device=device)
-        if "batch_index" in molecule and not torch.equal(molecule["batch_index"].to(device), batch_index):
-            raise ValueError("molecule['batch_index'] must be the contiguous index implied by molecule['num_nodes']")
-        dyn.plan(num_nodes.cpu())
-        N, D = int(batch_index.shape[0]), self.num_x_dims + self.num_node_scalar_features
-        parts = [molecule["x"], molecule["one_hot"]] + ([molecule["charges"]] if self.include_charges else [])
-        xh0 = torch.cat([p.to(device, torch.float32) for p in parts], dim=-1).contiguous()
-        fixed = node_mask_fixed.to(device).bool().contiguous()
-        if xh0.shape != (N, D) or fixed.shape != (N,):
-            raise ValueError(f"molecule has shape {tuple(xh0.shape)} / mask {tuple(fixed.shape)}, expected {(N, D)} / {(N,)}")
-        ctx_ptr = None
-        if context is not None:
-            context = context.to(device, torch.float32)[batch_index].contiguous()
-            ctx_ptr = C.c_void_p(context.data_ptr())
-        elif dyn.condition_on_context:
-            raise ValueError("context required by a context-conditioned model")
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        flags = torch.zeros(1, dtype=torch.int32, device=device)
-        fptr, sd = C.c_void_p(flags.data_ptr()), C.c_uint64(seed)
-        ptr = lambda t_: None if t_ is None else C.c_void_p(t_.data_ptr())       # noqa: E731
-        z = torch.empty((N, D), dtype=torch.float32, device=device)
-        frames = torch.zeros((return_frames, N, D), dtype=torch.float32, device=device)
-        self_cond = torch.zeros_like(z) if self_cond_on else None
-        k = 0
-        held: List[Optional[torch.Tensor]] = []
-
-        def draw():
-            """Tape tensor (kept alive until the stream has consumed it) or None = Philox draw number k."""
-            nonlocal k
-            nz = None if noise_fn is None else noise_fn(k).to(device, torch.float32).contiguous()
-            k += 1
-            held.append(nz)
-            return ptr(nz)
-
-        _native.check(lib, h, lib.gcdm_inpaint_center(h, ptr(xh0), ptr(fixed), ptr(xh0), stream), "gcdm_inpaint_center")
-        _native.check(lib, h, lib.gcdm_sample_init(h, ptr(z), draw(), sd, stream), "gcdm_sample_init")
         schedule = repaint_schedule(num_resamplings, jump_length, num_timesteps)
-        s = num_timesteps - 1
-        first = True
-        for i, num_denoise_steps in enumerate(schedule):
-            for j in range(num_denoise_steps):
-                base = k
-                p_known, p_unknown = draw(), draw()
-                p_sc = draw() if self_cond_on else None
-                st = lib.gcdm_inpaint_step(h, ptr(z), ptr(xh0), ptr(fixed), ptr(self_cond), int(not first), ctx_ptr, s, num_timesteps, p_known, p_unknown,
-                                           p_sc, sd, base, fptr, stream)
-                _native.check(lib, h, st, "gcdm_inpaint_step")
-                first = False
-                # frame at the end of a resample cycle (:1707-1715)
-                if return_frames > 1 and (num_denoise_steps > jump_length or i == len(schedule) - 1) and (s * return_frames) % num_timesteps == 0:
-                    fr = frames[(s * return_frames) // num_timesteps]
-                    _native.check(lib, h, lib.gcdm_unnormalize_z(h, ptr(z), ptr(fr), stream), "gcdm_unnormalize_z")
-                if j == num_denoise_steps - 1 and i < len(schedule) - 1:       # go back `jump_length` steps (:1717-1737)
-                    t = s + jump_length
-                    dk = k
-                    _native.check(lib, h, lib.gcdm_inpaint_jump(h, ptr(z), s, t, num_timesteps, draw(), sd, dk, stream), "gcdm_inpaint_jump")
-                    s = t
-                s -= 1
-        out = frames[0]
-        _native.check(lib, h, lib.gcdm_set_option(h, b"cog_fix", 1 if return_frames == 1 else 0), "gcdm_set_option")   # :1767
-        if self_cond_on:
-            st = lib.gcdm_sample_final_sc(h, ptr(z), ptr(self_cond) if not first else None, ctx_ptr, draw(), sd, ptr(out), fptr, stream)
-        else:
-            st = lib.gcdm_sample_final(h, ptr(z), ctx_ptr, draw(), sd, ptr(out), fptr, stream)
-        lib.gcdm_set_option(h, b"cog_fix", 1)
-        _native.check(lib, h, st, "gcdm_sample_final")
-        fl = int(flags.item())                                                  # the one host sync of the run
-        held.clear()
-        if fl & _native.FLAG_F16_RANGE and dyn.mfma_mode == 1:
-            if fl & _native.FLAG_TAIL:
-                dyn.disable_fused_layer("inpaint")
-            raise F16RangeError("an activation left the f16 range of the split-precision kernels during inpainting")
-        self._report_flags(fl, "inpaint")
-        return out if return_frames == 1 else frames
+        return self._rerun_in_fp32(lambda: fused_sampler.inpaint_once(self, molecule, node_mask_fixed, schedule, jump_length, return_frames,
+                                                                      num_timesteps, context, noise_fn, seed),
+                                   "the inpainting")
 
     def sample_p_zt_given_zs(self, zs, batch_index, node_mask, gamma_t, gamma_s, generate_x_only: bool = False, noise: Optional[torch.Tensor] = None,
                              generator: Optional[torch.Generator] = None):
@@ -1125,9 +828,7 @@ class EquivariantVariationalDiffusion(nn.Module):
         (so that a re-run after F16RangeError draws the same noise)."""
         device = torch.device(molecule["x"].device)
         nx = self.num_x_dims
-        if generate_x_only and getattr(self.dynamics_network, "num_atom_types", 0) + int(getattr(self.dynamics_network, "include_charges", False)) > 0:
-            raise ValueError("generate_x_only needs a dynamics network built without node features (num_atom_types = 0, include_charges = False); "
-                             "the reference fails on the feature width of this one too (gcpnet.py:1093-1110)")
+        self._check_x_only_network(generate_x_only)
         num_nodes = torch.as_tensor(molecule["num_nodes"])
         B = len(num_nodes)
         bi = num_nodes_to_batch_index(B, num_nodes.to(device), device=device)
@@ -1150,18 +851,7 @@ class EquivariantVariationalDiffusion(nn.Module):
             return sums / cnt[:, None]
 
         xh0[:, :nx] = xh0[:, :nx] - fixed_mean(xh0[:, :nx])[bi]                    # :1625-1633
-        k = [0]
-        gen = None
-        if noise_fn is None:
-            gen = torch.Generator(device=device)
-            gen.manual_seed(int(seed))
-
-        def draw():
-            if noise_fn is None:
-                return None
-            k[0] += 1
-            return noise_fn(k[0] - 1).to(device, torch.float32)
-
+        gen, draw = _module_draws(noise_fn, seed, device)
         raw = draw()
         if raw is None:
             z = self.sample_combined_position_feature_noise(bi, ones, generate_x_only=generate_x_only, generator=gen, num_graphs=B)
@@ -1202,54 +892,15 @@ class EquivariantVariationalDiffusion(nn.Module):
         x, h = self.sample_p_xh_given_z0(z_0=z, batch_index=bi, node_mask=ones, batch_size=B, context=context, generate_x_only=generate_x_only,
                                          xh_self_cond=self_cond, noise=draw(), generator=gen)
         self.assert_mean_zero_with_mask(x, ones)
-        if return_frames == 1:
-            cog = torch.zeros(B, nx, device=device).index_add_(0, bi, x).abs().max().item()
-            if cog > 5e-2:
-                x = _segment_mean_sub(x, bi, B, ones)
-        if generate_x_only:
-            out[0] = x
-        else:
-            out[0] = torch.cat([x, h["categorical"].to(x.dtype)] + ([h["integer"].to(x.dtype)] if self.include_charges else []), dim=-1)
+        out[0] = self._decoded_frame(x, h, bi, B, ones, return_frames, generate_x_only)
         # the device check word of the network evaluations of this loop (NaN in vel, ...; the range bit was handled by the deferred guard above)
         rf = getattr(self.dynamics_network, "read_flags", None)
         self.last_flags = (int(rf()) & ~_native.FLAG_F16_RANGE) if rf is not None and getattr(self.dynamics_network, "_handle", None) is not None else 0
         return out.squeeze(0)
 
     # ---- several independent batches in flight (evaluation driver) -------------------------------------------------------------
-    class _Lane:
-        """One extra library handle + stream: its own packed weights (26 MB) and workspace, so that the launches of different
-        batches are independent and the GPU can fill the CUs a 100-molecule batch leaves idle."""
-
-        def __init__(self, ddpm: "EquivariantVariationalDiffusion", device: torch.device):
-            dyn = ddpm.dynamics_network
-            self.lib = _native.load()
-            self.h = C.c_void_p()
-            idx = device.index if device.index is not None else torch.cuda.current_device()
-            cfg = dyn._native_config(idx)
-            _native.check(self.lib, self.h, self.lib.gcdm_create(C.byref(cfg), C.byref(self.h)), "gcdm_create")
-            for key, val in dyn.state_dict().items():
-                w = val.detach().to("cpu", torch.float32).contiguous()
-                _native.check(self.lib, self.h, self.lib.gcdm_set_weight(self.h, key.encode(), C.c_void_p(w.data_ptr()), w.numel()), "gcdm_set_weight")
-            _native.check(self.lib, self.h, self.lib.gcdm_finalize_weights(self.h), "gcdm_finalize_weights")
-            g = ddpm.gamma.gamma.detach().to("cpu", torch.float32).contiguous()
-            _native.check(self.lib, self.h, self.lib.gcdm_set_gamma(self.h, C.c_void_p(g.data_ptr()), g.numel()), "gcdm_set_gamma")
-            self.lib.gcdm_set_option(self.h, b"mfma_mode", dyn.mfma_mode)
-            # lane handles run CONCURRENTLY with other handles (slices of one batch, batches in flight): two launches per layer there -- the fused layer launch
-            # (option "fuse_node") packs a single handle's tiles better (-3 % per step), but beside another launch its node role is gated and loses (+3 %)
-            # (GCDM_LANE_FUSE=1: A/B hook.  Stream priorities for the slices -- lane 0 high, lane 1 normal, so that one slice's launch would be dispatched whole before
-            #  the other's -- were measured too: no effect on the dispatch interleave, 7.00 vs 7.00 ms per step un-fused, 7.21 vs 7.22 fused; profiles/r06_ab_log.txt)
-            self.lib.gcdm_set_option(self.h, b"fuse_node", int(os.environ.get("GCDM_LANE_FUSE", "0")))
-            self.stream = torch.cuda.Stream(device)
-            self.key = ddpm._lane_key(device)
-
-        def fresh(self, ddpm: "EquivariantVariationalDiffusion", device: torch.device) -> bool:
-            """Still a copy of the primary handle's weights / schedule / device?"""
-            return self.h is not None and self.key == ddpm._lane_key(device)
-
-        def close(self):
-            if self.h:
-                self.lib.gcdm_destroy(self.h)
-                self.h = None
+    _Lane = fused_sampler._Lane
+    _SlicedBatch = fused_sampler._SlicedBatch
 
     @torch.inference_mode()
     def mol_gen_sample_concurrent(self, num_nodes_list: List[torch.Tensor], device: Union[torch.device, str],
@@ -1258,71 +909,7 @@ class EquivariantVariationalDiffusion(nn.Module):
         """`mol_gen_sample` for several independent batches at once: batch b runs on its own handle and HIP stream, the step
         launches of all batches are interleaved on the host.  Results are those of `mol_gen_sample(..., seed=seeds[b])` called one
         after the other (bit-identical); small batches (the evaluation driver's 100 molecules) no longer leave CUs idle."""
-        device = torch.device(device)
-        K = len(num_nodes_list)
-        T = self.T if num_timesteps is None else num_timesteps
-        contexts = contexts if contexts is not None else [None] * K
-        seeds = seeds if seeds is not None else [1234 + b for b in range(K)]
-        self._native(device)                                   # validates the dynamics network, uploads the primary handle
-        lanes = self._get_lanes(K, device)
-        D = self.num_x_dims + self.num_node_scalar_features
-        work = []
-        for b in range(K):
-            ln = lanes[b]
-            nn_ = torch.as_tensor(num_nodes_list[b], dtype=torch.int32, device="cpu").contiguous()
-            _native.check(ln.lib, ln.h, ln.lib.gcdm_plan_batch(ln.h, len(nn_), C.c_void_p(nn_.data_ptr())), "gcdm_plan_batch")
-            bi = num_nodes_to_batch_index(len(nn_), nn_.to(device), device=device)
-            N = int(bi.shape[0])
-            ctx = contexts[b]
-            if ctx is not None:
-                ctx = ctx.to(device, torch.float32)[bi].contiguous()
-            elif self.dynamics_network.condition_on_context:
-                raise ValueError("context required by a context-conditioned model")
-            work.append(dict(lane=ln, bi=bi, z=torch.empty((N, D), dtype=torch.float32, device=device), out=torch.empty((N, D), dtype=torch.float32, device=device),
-                             flags=torch.zeros(1, dtype=torch.int32, device=device), ctx=ctx, seed=C.c_uint64(seeds[b])))
-        torch.cuda.synchronize(device)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        for w in work:
-            ln = w["lane"]
-            _native.check(ln.lib, ln.h, ln.lib.gcdm_sample_init(ln.h, ptr(w["z"]), None, w["seed"], C.c_void_p(ln.stream.cuda_stream)), "gcdm_sample_init")
-        for s in reversed(range(T)):
-            for w in work:
-                ln = w["lane"]
-                st = ln.lib.gcdm_sample_step(ln.h, ptr(w["z"]), ptr(w["ctx"]), s, T, None, w["seed"], ptr(w["flags"]), C.c_void_p(ln.stream.cuda_stream))
-                _native.check(ln.lib, ln.h, st, "gcdm_sample_step")
-        for w in work:
-            ln = w["lane"]
-            st = ln.lib.gcdm_sample_final(ln.h, ptr(w["z"]), ptr(w["ctx"]), None, w["seed"], ptr(w["out"]), ptr(w["flags"]), C.c_void_p(ln.stream.cuda_stream))
-            _native.check(ln.lib, ln.h, st, "gcdm_sample_final")
-        torch.cuda.synchronize(device)
-        results, fl_all = [], 0
-        for b, w in enumerate(work):
-            fl = int(w["flags"].item())
-            if fl & _native.FLAG_F16_RANGE:                    # rare: redo this batch on the primary handle (which falls back to fp32 MFMA)
-                log.warning("An activation left the f16 range in a concurrent batch; re-running it with fp32 MFMA.")
-                if fl & _native.FLAG_TAIL:
-                    self.dynamics_network.disable_fused_layer("mol_gen_sample_concurrent")
-                results.append(self.mol_gen_sample(len(num_nodes_list[b]), num_nodes_list[b], device, num_timesteps=T, context=contexts[b], seed=seeds[b]))
-                fl_all |= self.last_flags
-                continue
-            fl_all |= self._report_flags(fl, "mol_gen_sample_concurrent")
-            results.append((w["out"], w["bi"], torch.ones_like(w["bi"]).bool()))
-        self.last_flags = fl_all
-        return results
-
-    @staticmethod
-    def _check_batch_lists(num_nodes_list, contexts, seeds) -> None:
-        """Argument checks of the several-batches drivers that need no device: one context and one seed per batch, no empty batch."""
-        K = len(num_nodes_list)
-        if K == 0:
-            raise ValueError("num_nodes_list is empty: at least one batch is needed")
-        if len(contexts) != K:
-            raise ValueError(f"contexts has {len(contexts)} entries for {K} batches")
-        if len(seeds) != K:
-            raise ValueError(f"seeds has {len(seeds)} entries for {K} batches")
-        for b, nn_ in enumerate(num_nodes_list):
-            if len(nn_) == 0:
-                raise ValueError(f"batch {b} is empty: every batch needs at least one molecule")
+        return self._sample_batches(False, num_nodes_list, device, num_timesteps, contexts, seeds)
 
     @torch.inference_mode()
     def mol_gen_sample_packed(self, num_nodes_list: List[torch.Tensor], device: Union[torch.device, str],
@@ -1332,84 +919,29 @@ class EquivariantVariationalDiffusion(nn.Module):
         handle and sampled by one (captured) launch set per step.  Every batch stays a flat batch of its own -- orientation padding at its ends, its own
         noise stream, its own NaN-in-vel and CoG decisions -- so the results are those of `mol_gen_sample(..., seed=seeds[b])` called one after the other
         (bit-identical), at one copy of the weights and one workspace."""
+        return self._sample_batches(True, num_nodes_list, device, num_timesteps, contexts, seeds)
+
+    def _sample_batches(self, packed: bool, num_nodes_list, device, num_timesteps, contexts, seeds):
+        """The two samplers above behind their defaults.  The packed one checks what needs no device first: one context and one seed per batch, no
+        empty batch, no self-conditioned model."""
         K = len(num_nodes_list)
         contexts = contexts if contexts is not None else [None] * K
         seeds = seeds if seeds is not None else [1234 + b for b in range(K)]
-        self._check_batch_lists(num_nodes_list, contexts, seeds)
-        if bool(getattr(self.dynamics_network, "self_condition", False)):
-            raise NotImplementedError("mol_gen_sample_packed: a self-conditioned model is not served by a packed plan (the self-conditioned step entry points "
-                                      "refuse it); use mol_gen_sample per batch")
-        device = torch.device(device)
-        T = self.T if num_timesteps is None else num_timesteps
-        dyn, lib, h = self._native(device)
-        if dyn.condition_on_context and any(c is None for c in contexts):
-            raise ValueError("context required by a context-conditioned model")
-        sizes = [torch.as_tensor(nn_, dtype=torch.int32, device="cpu").reshape(-1) for nn_ in num_nodes_list]
-        per_batch = torch.tensor([len(sz) for sz in sizes], dtype=torch.int32)
-        nn_all = torch.cat(sizes).contiguous()
-        dyn._plan_key = None                   # the handle's plan is no longer one GCPNetDynamics.plan made: the next plan() call builds its own
-        dyn._plan_src = None
-        _native.check(lib, h, lib.gcdm_plan_batches(h, K, C.c_void_p(per_batch.data_ptr()), C.c_void_p(nn_all.data_ptr())), "gcdm_plan_batches")
-        sd = (C.c_uint64 * K)(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds])
-        _native.check(lib, h, lib.gcdm_set_batch_seeds(h, K, sd), "gcdm_set_batch_seeds")
-        bis = [num_nodes_to_batch_index(len(sz), sz.to(device), device=device) for sz in sizes]
-        node_off = [0]
-        for bi in bis:
-            node_off.append(node_off[-1] + int(bi.shape[0]))
-        N, D = node_off[-1], self.num_x_dims + self.num_node_scalar_features
-        ctx = None
-        if dyn.condition_on_context:
-            ctx = torch.cat([c.to(device, torch.float32)[bi] for c, bi in zip(contexts, bis)], dim=0).contiguous()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())           # noqa: E731
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        z = torch.empty((N, D), dtype=torch.float32, device=device)
-        out = torch.empty((N, D), dtype=torch.float32, device=device)
-        flags = torch.zeros(K, dtype=torch.int32, device=device)
-        no_seed = C.c_uint64(0)                # ignored under a packed plan
-        _native.check(lib, h, lib.gcdm_sample_init(h, ptr(z), None, no_seed, stream), "gcdm_sample_init")
-        for s in reversed(range(T)):
-            _native.check(lib, h, lib.gcdm_sample_step(h, ptr(z), ptr(ctx), s, T, None, no_seed, ptr(flags), stream), "gcdm_sample_step")
-        _native.check(lib, h, lib.gcdm_sample_final(h, ptr(z), ptr(ctx), None, no_seed, ptr(out), ptr(flags), stream), "gcdm_sample_final")
-        words = [int(v) for v in flags.cpu().tolist()]                             # the one host sync of a clean run
-        plan_wide = 0
-        for v in words:
-            plan_wide |= v
-        results, fl_all = [], 0
-        if plan_wide & _native.FLAG_F16_RANGE:     # rare, and plan-wide: redo every batch on the primary handle (which falls back to fp32 MFMA)
-            log.warning("An activation left the f16 range in a packed run; re-running its batches with fp32 MFMA.")
-            if plan_wide & _native.FLAG_TAIL:
-                dyn.disable_fused_layer("mol_gen_sample_packed")
-            for b in range(K):
-                results.append(self.mol_gen_sample(len(sizes[b]), num_nodes_list[b], device, num_timesteps=T, context=contexts[b], seed=seeds[b]))
-                fl_all |= self.last_flags
-            self.last_flags = fl_all
-            return results
-        for b in range(K):
-            fl_all |= self._report_flags(words[b], "mol_gen_sample_packed")
-            results.append((out[node_off[b]:node_off[b + 1]], bis[b], torch.ones_like(bis[b]).bool()))
-        self.last_flags = fl_all
-        return results
-
-    def _lane_key(self, device: torch.device):
-        dyn = self.dynamics_network
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        g = self.gamma.gamma
-        return (dyn._params_fingerprint(), idx, g.data_ptr(), g._version)
-
-    def _get_lanes(self, K: int, device: torch.device):
-        """K extra handles that mirror the primary one.  A lane is a COPY of the weights: after load_state_dict / an EMA swap / fine-tuning /
-        `.to(other device)` the stale ones are rebuilt (the primary handle re-uploads through sync_weights)."""
-        lanes = [ln for ln in (getattr(self, "_lanes", None) or [])]
-        for i, ln in enumerate(lanes):
-            if not ln.fresh(self, device):
-                ln.close()
-                lanes[i] = self._Lane(self, device)
-        while len(lanes) < K:
-            lanes.append(self._Lane(self, device))
-        for ln in lanes:
-            ln.lib.gcdm_set_option(ln.h, b"mfma_mode", self.dynamics_network.mfma_mode)
-        self._lanes = lanes
-        return lanes
+        if packed:
+            if K == 0:
+                raise ValueError("num_nodes_list is empty: at least one batch is needed")
+            if len(contexts) != K:
+                raise ValueError(f"contexts has {len(contexts)} entries for {K} batches")
+            if len(seeds) != K:
+                raise ValueError(f"seeds has {len(seeds)} entries for {K} batches")
+            for b, nn_ in enumerate(num_nodes_list):
+                if len(nn_) == 0:
+                    raise ValueError(f"batch {b} is empty: every batch needs at least one molecule")
+            if bool(getattr(self.dynamics_network, "self_condition", False)):
+                raise NotImplementedError("mol_gen_sample_packed: a self-conditioned model is not served by a packed plan (the self-conditioned step entry "
+                                          "points refuse it); use mol_gen_sample per batch")
+        return fused_sampler.sample_batches(self, num_nodes_list, torch.device(device), self.T if num_timesteps is None else num_timesteps,
+                                            contexts, seeds, packed)
 
     def release_lanes(self):
         for ln in getattr(self, "_lanes", None) or []:
@@ -1421,149 +953,6 @@ class EquivariantVariationalDiffusion(nn.Module):
             self.release_lanes()
         except Exception:
             pass
-
-    class _SlicedBatch:
-        """One flat batch sampled as K contiguous slices of molecules, each on its own handle and HIP stream (same semantics and the
-        same Philox noise as the single-handle run: a slice's boundary nodes read their flat neighbours from the adjacent slice,
-        options "flat_prev" / "flat_next" / "node_base").  The latent is double-buffered (`gcdm_sample_step_to`) and the slices join
-        once per step, so no slice ever reads a row its neighbour is writing.  Fills the round-quantisation tails of the big
-        configurations (+5-6 % at 1024 QM9 / 256 GEOM molecules on MI355X)."""
-
-        def __init__(self, ddpm: "EquivariantVariationalDiffusion", num_nodes, device: torch.device, context: Optional[torch.Tensor], seed: int, K: int):
-            self.ddpm, self.device, self.K = ddpm, device, K
-            dyn, lib, h0 = ddpm._native(device)
-            self.dyn = dyn
-            nn_ = torch.as_tensor(num_nodes, dtype=torch.int32, device="cpu")
-            Bm = len(nn_)
-            cuts = slice_cuts(nn_, K)
-            self.cuts = cuts
-            self.node_off = torch.cat((torch.zeros(1, dtype=torch.long), nn_.long().cumsum(0))).tolist()
-            lanes = ddpm._get_lanes(K, device)
-            self.batch_index = num_nodes_to_batch_index(Bm, nn_.to(device), device=device)
-            N, D = int(self.batch_index.shape[0]), ddpm.num_x_dims + ddpm.num_node_scalar_features
-            self.ctx = None
-            if context is not None:
-                self.ctx = context.to(device, torch.float32)[self.batch_index].contiguous()
-            elif dyn.condition_on_context:
-                raise ValueError("context required by a context-conditioned model")
-            self.bufs = [torch.empty((N, D), dtype=torch.float32, device=device) for _ in range(2)]
-            self.out = torch.empty((N, D), dtype=torch.float32, device=device)
-            self.flags = torch.zeros(K, dtype=torch.int32, device=device)
-            self.sd = C.c_uint64(seed)
-            self.sl = []
-            for k in range(K):
-                ln = lanes[k]
-                part = nn_[cuts[k]:cuts[k + 1]].contiguous()
-                _native.check(ln.lib, ln.h, ln.lib.gcdm_plan_batch(ln.h, len(part), C.c_void_p(part.data_ptr())), "gcdm_plan_batch")
-                n0 = self.node_off[cuts[k]]
-                for name, val in ((b"flat_prev", int(k > 0)), (b"flat_next", int(k < K - 1)), (b"node_base", n0), (b"mfma_mode", dyn.mfma_mode)):
-                    _native.check(ln.lib, ln.h, ln.lib.gcdm_set_option(ln.h, name, val), "gcdm_set_option")
-                self.sl.append(dict(lane=ln, n0=n0, stream=C.c_void_p(ln.stream.cuda_stream), ev=torch.cuda.Event(),
-                                    fl=C.c_void_p(self.flags.data_ptr() + 4 * k)))
-            self.cur = 0
-
-        @staticmethod
-        def _row(t_, n0):
-            return C.c_void_p(t_.data_ptr() + 4 * n0 * t_.shape[1])
-
-        def _cptr(self, n0):
-            return None if self.ctx is None else self._row(self.ctx, n0)
-
-        def _join(self):
-            for a_ in self.sl:
-                for b_ in self.sl:
-                    if a_ is not b_:
-                        a_["lane"].stream.wait_event(b_["ev"])
-
-        def init(self):
-            start = torch.cuda.Event()
-            start.record(torch.cuda.current_stream(self.device))
-            for w in self.sl:
-                ln = w["lane"]
-                ln.stream.wait_event(start)
-                _native.check(ln.lib, ln.h, ln.lib.gcdm_sample_init(ln.h, self._row(self.bufs[0], w["n0"]), None, self.sd, w["stream"]), "gcdm_sample_init")
-                w["ev"].record(ln.stream)
-            self.cur = 0
-
-        def step(self, s: int, t_norm: int):
-            self._join()
-            cur, nxt = self.cur, 1 - self.cur
-            for w in self.sl:
-                ln = w["lane"]
-                st = ln.lib.gcdm_sample_step_to(ln.h, self._row(self.bufs[cur], w["n0"]), self._row(self.bufs[nxt], w["n0"]), self._cptr(w["n0"]), s, t_norm,
-                                                None, self.sd, w["fl"], w["stream"])
-                _native.check(ln.lib, ln.h, st, "gcdm_sample_step_to")
-                w["ev"].record(ln.stream)
-            self.cur = nxt
-
-        def final(self):
-            self._join()
-            for w in self.sl:
-                ln = w["lane"]
-                st = ln.lib.gcdm_sample_final(ln.h, self._row(self.bufs[self.cur], w["n0"]), self._cptr(w["n0"]), None, self.sd, self._row(self.out, w["n0"]),
-                                              w["fl"], w["stream"])
-                _native.check(ln.lib, ln.h, st, "gcdm_sample_final")
-                w["ev"].record(ln.stream)
-            self.wait()
-
-        def wait(self):
-            """The caller's current stream waits for every slice (no host sync)."""
-            cs = torch.cuda.current_stream(self.device)
-            for w in self.sl:
-                cs.wait_event(w["ev"])
-
-        def close(self):
-            for w in self.sl:                                   # lanes go back to whole-batch behaviour
-                for name in (b"flat_prev", b"flat_next", b"node_base"):
-                    w["lane"].lib.gcdm_set_option(w["lane"].h, name, 0)
-
-        def recentre_undrifted(self, drift: List[bool]):
-            """The reference re-projects the WHOLE batch when any molecule drifted (:1389-1402): slices that saw no drift follow."""
-            for k, w in enumerate(self.sl):
-                if not drift[k]:
-                    n0, n1 = w["n0"], self.node_off[self.cuts[k + 1]]
-                    bi = self.batch_index[n0:n1] - self.batch_index[n0]
-                    cnt = torch.bincount(bi).clamp(min=1).to(torch.float32)[:, None]
-                    mean = torch.zeros((int(bi.max()) + 1, 3), device=self.device).index_add_(0, bi, self.out[n0:n1, :3]) / cnt
-                    self.out[n0:n1, :3] -= mean[bi]
-
-    @torch.inference_mode()
-    def _mol_gen_sample_lanes(self, num_samples, num_nodes, device, num_timesteps, t_norm, context, seed, K):
-        device = torch.device(device)
-        sb = self._SlicedBatch(self, num_nodes, device, context, seed, K)
-        cs = torch.cuda.current_stream(device)
-        fl_all = []
-
-        def fence():                         # the slices continue only after what the caller's stream has just done with their buffers
-            ev = torch.cuda.Event()
-            ev.record(cs)
-            for w in sb.sl:
-                w["lane"].stream.wait_event(ev)
-
-        def final():
-            sb.final()
-            fl_all[:] = sb.flags.cpu().tolist()             # the one host sync of a clean run
-            fl = 0
-            for v in fl_all:
-                fl |= int(v)
-            return fl
-
-        def set_mode(mode):
-            for w in sb.sl:
-                w["lane"].lib.gcdm_set_option(w["lane"].h, b"mfma_mode", mode)
-
-        guard = _RangeCheckpoints(active=sb.dyn.mfma_mode == 1)
-        try:
-            sb.init()
-            fl = guard.run(num_timesteps, lambda s: sb.step(s, t_norm), final, sb.flags, lambda: ({}, [sb.bufs[sb.cur]]),
-                           lambda st, copies: sb.bufs[sb.cur].copy_(copies[0]), set_mode, wait=sb.wait, fence=fence)
-        finally:
-            sb.close()
-        self._report_flags(fl, "mol_gen_sample", guard)
-        drift = [bool(int(v) & _native.FLAG_COG_DRIFT) for v in fl_all]
-        if any(drift) and not all(drift):
-            sb.recentre_undrifted(drift)
-        return sb.out, sb.batch_index, torch.ones_like(sb.batch_index).bool()
 
     def get_repaint_schedule(self, resamplings: int, jump_length: int, num_timesteps: int) -> List[int]:
         """variational_diffusion.py:1548-1578."""
