@@ -24,7 +24,8 @@ OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(
                os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.classifier.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.objective.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_objective.h"),
-               os.path.join(_HERE, "csrc", "gcdm_ops.bucket.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_grad_bucket.h")]
+               os.path.join(_HERE, "csrc", "gcdm_ops.bucket.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_grad_bucket.h"),
+               os.path.join(os.path.dirname(_HERE), "include", "gcdm_matrix_mode.h")]
 ABI_VERSION = 2
 
 FLAG_NAN_VEL, FLAG_MEAN_NOT_ZERO, FLAG_COG_DRIFT, FLAG_F16_RANGE = 1, 2, 4, 8
@@ -193,6 +194,13 @@ GRAD_BUCKET_SIGNATURES = {
 }
 GRAD_BUCKET_RESTYPES = {"gcdm_grad_bucket_floats": C.c_int64}
 GRAD_BUCKET_FLAG_MISMATCH = 2   # GCDM_GRAD_BUCKET_FLAG_MISMATCH
+# the matrix mode of the training GEMMs (include/gcdm_matrix_mode.h), exported from the same library; neither entry makes a HIP call
+MATRIX_MODE_SIGNATURES = {
+    "gcdm_ops_set_matrix_mode": [I32],
+    "gcdm_ops_get_matrix_mode": [],
+}
+MATRIX_MODE_RESTYPES = {"gcdm_ops_get_matrix_mode": C.c_int32}
+MATRIX_MODES = {"f32": 0, "bf16x6": 1}          # GCDM_OPS_MATRIX_F32, GCDM_OPS_MATRIX_BF16X6
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -208,6 +216,10 @@ def load_ops() -> C.CDLL:
         fn = getattr(lib, name)
         fn.argtypes = sig
         fn.restype = {**MP_TRAIN_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
+    for name, sig in MATRIX_MODE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = sig
+        fn.restype = MATRIX_MODE_RESTYPES.get(name, C.c_int)
     _ops_lib = lib
     return lib
 

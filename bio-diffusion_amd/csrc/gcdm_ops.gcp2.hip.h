@@ -164,12 +164,18 @@ __global__ __launch_bounds__(256) void k_gcp2_down(Dims d, const float* __restri
 
 // ---- forward: p = A W^T + b over all SO columns of 64 rows, s_out = act0(p), gate = act1(p) W_g^T + b_g, v_out *= sigmoid(gate) ----------------
 // A = X (lda = K) or, with ASILU, silu(hid) (lda = SO).  v_out holds vector_up(vh) on entry (k_gcp2_down).
-template <int ASILU>
+// In bf16x6 mode (MODE, gcdm_ops.tile.hip.h) the gate contraction is a second pass of the tile body over Ps, so its operands are split like any other's.
+struct PsA {
+    const float (*Ps)[GM + 1];
+    int64_t m0;
+    int n0;
+    __device__ __forceinline__ float operator()(int64_t r, int64_t k) const { return Ps[k - n0][r - m0]; }
+};
+template <int ASILU, int MODE>
 __global__ __launch_bounds__(256) void k_gcp2_scalar(Dims d, const float* __restrict__ A, int64_t Kd, const float* __restrict__ W, const float* __restrict__ bias,
                                                      const float* __restrict__ Wg, const float* __restrict__ bg, float* __restrict__ p_out,
                                                      float* __restrict__ s_out, float* __restrict__ gate_out, float* __restrict__ v_out) {
-    __shared__ float As[2][GK][GM + 1];
-    __shared__ float Bs[2][GK][GN + 1];
+    __shared__ typename TileLds<MODE>::type As[2], Bs[2];
     __shared__ float Ps[GN][GM + 1];                       // act1(p) of the current column tile, [column][row]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave & 1, wn = wave >> 1;
@@ -178,7 +184,7 @@ __global__ __launch_bounds__(256) void k_gcp2_scalar(Dims d, const float* __rest
     const FunctorA<RowMajorA<ASILU>> aload{{A, Kd}};
     f32x16 gacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int n0 = 0; n0 < d.SO; n0 += GN) {
-        const f32x16 acc = tile_mma(aload, W, 1, Kd, m0, n0, d.M, d.SO, 0, Kd, As, Bs);
+        const f32x16 acc = tile_body<MODE>(aload, W, 1, Kd, m0, n0, d.M, d.SO, 0, Kd, As, Bs);
         const int col = n0 + cl;
         const bool cv = col < d.SO;
         const float bv = cv ? bias[col] : 0.f;
@@ -194,7 +200,14 @@ __global__ __launch_bounds__(256) void k_gcp2_scalar(Dims d, const float* __rest
             }
             if (d.VO) Ps[cl][rl] = ok ? act_f(act_kind(d.a1), pv) : 0.f;
         }
-        if (d.VO) {
+        if constexpr (MODE == MM_BF16X6) {
+            if (d.VO) {
+                __syncthreads();
+                // gate[m][c] += sum_k Ps[k][m] W_g[c][n0 + k]: B(k, n = c) = W_g[c * SO + k], k in [n0, min(n0 + GN, SO))
+                const int k1 = n0 + GN < d.SO ? n0 + GN : d.SO;
+                gacc += tile_body<MODE>(FunctorA<PsA>{{Ps, m0, n0}}, Wg, 1, d.SO, m0, 0, d.M, d.VO, n0, k1, As, Bs);
+            }
+        } else if (d.VO) {
             __syncthreads();
             const bool gv = cl < d.VO;
             const float* wg = Wg + (int64_t)(gv ? cl : 0) * d.SO + n0;
@@ -252,19 +265,19 @@ struct DgateA {
         return dg;
     }
 };
+template <int MODE>
 __global__ __launch_bounds__(256) void k_gcp2_gate_bwd(Dims d, const float* __restrict__ ds_out, const float* __restrict__ dv_out, const float* __restrict__ p,
                                                        const float* __restrict__ vh, const float* __restrict__ gate, const float* __restrict__ wup,
                                                        const float* __restrict__ Wg, float* __restrict__ dup, float* __restrict__ dgate,
                                                        float* __restrict__ dp, float* __restrict__ ga, float* __restrict__ one) {
-    __shared__ float As[2][GK][GM + 1];
-    __shared__ float Bs[2][GK][GN + 1];
+    __shared__ typename TileLds<MODE>::type As[2], Bs[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int64_t m0 = (int64_t)blockIdx.x * GM;
     const int n0 = blockIdx.y * GN;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *one = 1.f;
     const FunctorA<DgateA> aload{{vh, wup, gate, dv_out, dup, dgate, d.H, d.VO, blockIdx.y == 0}};
-    const f32x16 acc = tile_mma(aload, Wg, d.SO, 1, m0, n0, d.M, d.SO, 0, d.VO, As, Bs);      // B(k = c, n) = W_g[c][n]
+    const f32x16 acc = tile_body<MODE>(aload, Wg, d.SO, 1, m0, n0, d.M, d.SO, 0, d.VO, As, Bs);      // B(k = c, n) = W_g[c][n]
     const int col = n0 + wn * 32 + (lane & 31);
     if (col >= d.SO) return;
 #pragma unroll
@@ -284,16 +297,16 @@ __global__ __launch_bounds__(256) void k_gcp2_gate_bwd(Dims d, const float* __re
 }
 
 // ---- backward, feedforward_out: dhid = (dp W2) silu'(hid), a2 = silu(hid) -----------------------------------------------------------------------
+template <int MODE>
 __global__ __launch_bounds__(256) void k_gcp2_ff_bwd(Dims d, const float* __restrict__ dp, const float* __restrict__ W2, const float* __restrict__ hid,
                                                      float* __restrict__ dhid, float* __restrict__ a2) {
-    __shared__ float As[2][GK][GM + 1];
-    __shared__ float Bs[2][GK][GN + 1];
+    __shared__ typename TileLds<MODE>::type As[2], Bs[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int64_t m0 = (int64_t)blockIdx.x * GM;
     const int n0 = blockIdx.y * GN;
     const FunctorA<RowMajorA<0>> aload{{dp, d.SO}};
-    const f32x16 acc = tile_mma(aload, W2, d.SO, 1, m0, n0, d.M, d.SO, 0, d.SO, As, Bs);       // B(k, n) = W2[k][n]
+    const f32x16 acc = tile_body<MODE>(aload, W2, d.SO, 1, m0, n0, d.M, d.SO, 0, d.SO, As, Bs);       // B(k, n) = W2[k][n]
     const int col = n0 + wn * 32 + (lane & 31);
     if (col >= d.SO) return;
 #pragma unroll
@@ -418,6 +431,8 @@ int gcdm_gcp2_fwd(const float* s, const float* v, const float* F, const uint8_t*
     GOPS_REQUIRE(s && v && F && s_out && workspace && (v_out || !d.VO) && ggcp_weights_ok(weights, wi.n));
     const float* const* W = weights;
     const hipStream_t st = (hipStream_t)stream;
+    const int mode = gops_matrix_mode();         // read once: every GEMM launch of this call runs in it
+    auto gemm = [&](auto... a) { gops::gemm(a..., 1, mode); };
     const FwdLayout L = fwd_layout(d, tape);
     float* ws = workspace;
     float* X = ws + L.x;
@@ -432,9 +447,9 @@ int gcdm_gcp2_fwd(const float* s, const float* v, const float* F, const uint8_t*
     if (d.ff) {
         float* hid = ws + L.hid;
         gemm(X, d.K, 1, W[wi.ws], 1, d.K, hid, W[wi.bs], M, d.SO, d.K, st);                         // hid = X W0^T + b0
-        hipLaunchKernelGGL(k_gcp2_scalar<1>, rows, dim3(256), 0, st, d, (const float*)hid, (int64_t)d.SO, W[wi.w2], W[wi.b2], wg, bg, p, s_out, gate, v_out);
+        GOPS_LAUNCH_MODE2(mode, k_gcp2_scalar, 1, rows, dim3(256), 0, st, d, (const float*)hid, (int64_t)d.SO, W[wi.w2], W[wi.b2], wg, bg, p, s_out, gate, v_out);
     } else {
-        hipLaunchKernelGGL(k_gcp2_scalar<0>, rows, dim3(256), 0, st, d, (const float*)X, (int64_t)d.K, W[wi.ws], W[wi.bs], wg, bg, p, s_out, gate, v_out);
+        GOPS_LAUNCH_MODE2(mode, k_gcp2_scalar, 0, rows, dim3(256), 0, st, d, (const float*)X, (int64_t)d.K, W[wi.ws], W[wi.bs], wg, bg, p, s_out, gate, v_out);
     }
     return GOPS_LAUNCH_OK();
 }
@@ -451,6 +466,8 @@ int gcdm_gcp2_bwd(const float* ds_out, const float* dv_out, const float* s, cons
     (void)s;                                   // the merged row on the tape holds it
     const float* const* W = weights;
     const hipStream_t st = (hipStream_t)stream;
+    const int mode = gops_matrix_mode();         // read once: every GEMM launch of this call runs in it
+    auto gemm = [&](auto... a) { gops::gemm(a..., 1, mode); };
     const FwdLayout T = fwd_layout(d, 1);
     const BwdLayout L = bwd_layout(d);
     const float* t = tape;
@@ -461,11 +478,11 @@ int gcdm_gcp2_bwd(const float* ds_out, const float* dv_out, const float* s, cons
     float* dgate = d.VO ? ws + L.dgate : nullptr;
     float* ga = d.VO ? ws + L.ga : nullptr;
     const dim3 tiles((unsigned)((M + GM - 1) / GM), (unsigned)((d.SO + GN - 1) / GN));
-    hipLaunchKernelGGL(k_gcp2_gate_bwd, tiles, dim3(256), 0, st, d, ds_out, dv_out, t + T.p, vh, d.VO ? t + T.gate : nullptr, wup,
+    GOPS_LAUNCH_MODE(mode, k_gcp2_gate_bwd, tiles, dim3(256), 0, st, d, ds_out, dv_out, t + T.p, vh, d.VO ? t + T.gate : nullptr, wup,
                        d.VO ? W[wi.wg] : nullptr, dup, dgate, ws + L.dp, ga, ws + L.one);
     const float* dpre = ws + L.dp;             // the gradient of what scalar_out's first Linear produced
     if (d.ff) {
-        hipLaunchKernelGGL(k_gcp2_ff_bwd, tiles, dim3(256), 0, st, d, (const float*)(ws + L.dp), W[wi.w2], t + T.hid, ws + L.dhid, ws + L.a2);
+        GOPS_LAUNCH_MODE(mode, k_gcp2_ff_bwd, tiles, dim3(256), 0, st, d, (const float*)(ws + L.dp), W[wi.w2], t + T.hid, ws + L.dhid, ws + L.a2);
         dpre = ws + L.dhid;
     }
     gemm(dpre, d.SO, 1, W[wi.ws], d.K, 1, ws + L.dx, nullptr, M, d.K, d.SO, st);                       // dX = dpre . W_s
@@ -492,7 +509,7 @@ int gcdm_gcp2_bwd(const float* ds_out, const float* dv_out, const float* s, cons
         G.add(dgate, 1, d.VO, ga, d.SO, 1, d.VO, d.SO, M, off[wi.wg], d.SO);                                 // dW_gate = dgate^T act1(p)
         G.add(dgate, 1, d.VO, one, 0, 0, d.VO, 1, M, off[wi.bg], 1);
     }
-    wgrad_launch(G, ws + L.part, dweights, st);
+    wgrad_launch(G, ws + L.part, dweights, st, mode);
     return GOPS_LAUNCH_OK();
 }
 

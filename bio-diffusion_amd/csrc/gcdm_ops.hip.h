@@ -14,6 +14,8 @@
 // frames [M][9] = rows a, b, c of f_ij.  All fp32.  No fallback: a launch failure is reported through the int status.
 #pragma once
 #include "gcdm_ops.tile.hip.h"
+#include "../../include/gcdm_matrix_mode.h"
+#include <atomic>
 
 namespace gops {
 
@@ -280,6 +282,9 @@ static inline unsigned gops_blocks(int64_t n, int t = 256) { return (unsigned)((
 // empty work is 0 without a launch
 #define GOPS_REQUIRE(cond) do { if (!(cond)) return -1; } while (0)
 static inline bool gops_flag(int32_t v) { return v == 0 || v == 1; }
+// the process-wide matrix mode (include/gcdm_matrix_mode.h): one atomic word, so the autograd thread sees what the caller's thread set
+static std::atomic<int32_t> g_gops_matrix_mode{gops::MM_F32};
+static inline int gops_matrix_mode() { return g_gops_matrix_mode.load(std::memory_order_acquire); }
 
 extern "C" {
 
@@ -288,9 +293,15 @@ int gcdm_op_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64
     GOPS_REQUIRE(M >= 0 && N >= 0 && K >= 0 && slices >= 1);
     if (M == 0 || N == 0) return 0;
     GOPS_REQUIRE(A && B && C);
-    gops::gemm(A, sam, sak, B, sbk, sbn, C, bias, M, N, K, (hipStream_t)stream, slices);
+    gops::gemm(A, sam, sak, B, sbk, sbn, C, bias, M, N, K, (hipStream_t)stream, slices, gops_matrix_mode());
     return GOPS_LAUNCH_OK();
 }
+int gcdm_ops_set_matrix_mode(int32_t mode) {
+    GOPS_REQUIRE(mode == gops::MM_F32 || mode == gops::MM_BF16X6);
+    g_gops_matrix_mode.store(mode, std::memory_order_release);
+    return 0;
+}
+int32_t gcdm_ops_get_matrix_mode(void) { return gops_matrix_mode(); }
 int gcdm_op_reduce_slices(const float* part, float* out, int64_t n, int32_t slices, void* stream) {
     GOPS_REQUIRE(n >= 0 && slices >= 1);
     if (n == 0) return 0;

@@ -424,6 +424,8 @@ int gcdm_mp_fwd(const float* h, const float* vnode, const float* e, const float*
     const float* const* W = weights;
     const hipStream_t st = (hipStream_t)stream;
     const Dims d = make_dims(N, E, SE, VE);
+    const int mode = gops_matrix_mode();         // read once: every GEMM launch of this call runs in it
+    auto gemm = [&](auto... a) { gops::gemm(a..., 1, mode); };
     const FwdLayout L = fwd_layout(d, tape);
     float* ws = workspace;
     float* sfin = ws + fwd_sfin(L);
@@ -466,6 +468,8 @@ int gcdm_mp_bwd(const float* dagg, const float* h, const int64_t* row, const int
     const float* const* W = weights;
     const hipStream_t st = (hipStream_t)stream;
     const Dims d = make_dims(N, E, SE, VE);
+    const int mode = gops_matrix_mode();         // read once: every GEMM launch of this call runs in it
+    auto gemm = [&](auto... a) { gops::gemm(a..., 1, mode); };
     const FwdLayout F = fwd_layout(d, 1);
     const BwdLayout L = bwd_layout(d);
     const float* t = tape;
@@ -518,7 +522,7 @@ int gcdm_mp_bwd(const float* dagg, const float* h, const int64_t* row, const int
     }
     T.add(ws + L.dlog, 0, 1, t + fwd_sfin(F), S, 1, 1, S, E, off[28], S);                                     // attention weight
     T.add(ws + L.dlog, 0, 1, one, 0, 0, 1, 1, E, off[29], 1);                                                 // attention bias
-    wgrad_launch(T, ws + L.part, dweights, st);
+    wgrad_launch(T, ws + L.part, dweights, st, mode);
     return GOPS_LAUNCH_OK();
 }
 

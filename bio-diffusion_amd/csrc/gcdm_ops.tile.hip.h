@@ -5,7 +5,9 @@
 //
 // A kernel on the tile body is index setup, one tile_mma() call, its own epilogue.  The MFMAs of a tile run over k in ascending order, two k
 // per instruction, whoever calls: that fixed order is what makes every operator's result independent of the row count and the same bits from
-// run to run.
+// run to run.  A second body with the same contract, tile_mma_bf16x6 (six v_mfma_f32_32x32x16_bf16 per 16-deep block on three bf16 images of
+// every fp32 element), serves the opt-in bf16x6 matrix mode (include/gcdm_matrix_mode.h); the kernels take the mode as a template parameter
+// and reach either body through tile_body<MODE>, the fp32 instantiation being the kernel as it was before the mode existed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +22,25 @@ constexpr int GM = 64, GN = 64, GK = 16;
 // ---- the A operand of a tile: where element i (of 4 per thread and K step) comes from ---------------------------------------------------------
 // Strided: A[row * sam + k * sak].  The element address is set up once and advanced by GK * sak per K step (round 3: a pointer += stride
 // instead of two 64-bit multiplies per element and step); the thread-to-element coordinates follow the fast axis (coalesced either way).
+// (start4 / get4: the same operand for the bf16x6 body below, which takes 4 consecutive k of one row per thread and K step.)
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+// x[i] = element k + i of one row or column of a strided operand, p at its element k, k stride sk: 0 and not dereferenced where the row
+// is invalid or k + i >= k_end.  A k-contiguous quadruple that lies inside the range is ONE 16-byte load, which needs dword alignment
+// only, so odd row strides (K = 273) and bases off by one float take it too.
+__device__ __forceinline__ void strided_load4(const float* p, int64_t sk, bool valid, int64_t k, int64_t k_end, float (&x)[4]) {
+    if (valid && k + 3 < k_end) {
+        if (sk == 1) {
+            const f32x4u v = *reinterpret_cast<const f32x4u*>(p);
+            x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[i] = p[i * sk];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = (valid && k + i < k_end) ? p[i * sk] : 0.f;
+    }
+}
 struct StridedA {
     const float* A;
     int64_t sam, sak;
@@ -31,6 +52,11 @@ struct StridedA {
         p[i] += GK * sak;
         return x;
     }
+    __device__ __forceinline__ void start4(bool valid, int64_t row, int64_t k) { start(0, valid, row, k); }
+    __device__ __forceinline__ void get4(bool valid, int64_t, int64_t k, int64_t k_end, float (&x)[4]) {
+        strided_load4(p[0], sak, valid, k, k_end, x);
+        p[0] += GK * sak;
+    }
 };
 // Computed: f(row, k), addressed k-fast.  f is called exactly once per element of a K step, by exactly one thread, and never outside
 // [0, M) x [k_begin, k_end) -- it may write what it computed as a side effect.
@@ -40,6 +66,11 @@ struct FunctorA {
     __device__ __forceinline__ bool kfast() const { return true; }
     __device__ __forceinline__ void start(int, bool, int64_t, int64_t) {}
     __device__ __forceinline__ float get(int, bool ok, int64_t row, int64_t k) { return ok ? f(row, k) : 0.f; }
+    __device__ __forceinline__ void start4(bool, int64_t, int64_t) {}
+    __device__ __forceinline__ void get4(bool valid, int64_t row, int64_t k, int64_t k_end, float (&x)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = (valid && k + i < k_end) ? f(row, k + i) : 0.f;
+    }
 };
 
 // ---- one 64 x 64 tile of A[M,K] . B[K,N] over k in [k_begin, k_end) -----------------------------------------------------------------------------
@@ -103,20 +134,123 @@ __device__ __forceinline__ f32x16 tile_mma(ASrc a, const float* __restrict__ B, 
 // element r of a lane's accumulator is row tile_row(wm, lane, r) of the tile (wm = wave & 1), column (wave >> 1) * 32 + (lane & 31)
 __device__ __forceinline__ int tile_row(int wm, int lane, int r) { return wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
+// ---- the same tile in bf16x6 mode (include/gcdm_matrix_mode.h): six v_mfma_f32_32x32x16_bf16 per 16-deep block ----------------------------------
+// Every fp32 element is the exact sum of three bf16 images, x = x0 + x1 + x2 (x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1), round to
+// nearest even: 3 x 8 significand bits, both subtractions exact), and
+//     x y ~ x0 y0 + (x0 y1 + x1 y0) + (x1 y1 + x0 y2 + x2 y0)                       (dropped: x1 y2, x2 y1, x2 y2 <= 2^-24 relative)
+// Products of bf16 values are exact in fp32 and the MFMA accumulates in fp32, in three accumulators (one per bracket) that are merged once at
+// the end, smallest first.  bf16 has fp32's exponent range, so there is no prescale, no range guard and no flag: an operand that is not
+// finite or is >= 2^127 in magnitude becomes NaN in all three images (below 2^127 no image can round up to Inf) and so does every output
+// element that depends on it.
+// The split happens once per workgroup where the element is stashed: a thread takes 4 consecutive k of one row (A) / column (B) per K step,
+// splits them and writes 8 bytes per image; the images are k-contiguous in LDS, [image][k / 8][row][k % 8] (16-byte chunks: the ds_read_b128 of
+// a wave's 32 rows x 2 k-halves falls on 16 distinct chunks per 16-lane group), so an MFMA operand is one ds_read_b128 per image and the
+// conversion results reach the MFMAs through LDS only.  Same contract as tile_mma otherwise: k ascending in steps of GK, rows >= M, columns
+// >= N and k outside [k_begin, k_end) read as 0 and are never dereferenced, a row's bits depend on that row alone, f32x16 result in
+// tile_row()'s layout.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+struct alignas(16) X6Tile {
+    u32x2 c[3][GK / 8][GM][2];             // [image][k / 8][row][(k / 4) & 1]: 4 bf16 each
+};
+__device__ __forceinline__ void x6_split4(const float (&x)[4], u32x2 (&img)[3]) {
+    bf16x4 b0, b1, b2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float v = __builtin_fabsf(x[i]) < 0x1p127f ? x[i] : __builtin_nanf("");
+        b0[i] = (__bf16)v;
+        const float r1 = v - (float)b0[i];
+        b1[i] = (__bf16)r1;
+        b2[i] = (__bf16)(r1 - (float)b1[i]);
+    }
+    img[0] = __builtin_bit_cast(u32x2, b0); img[1] = __builtin_bit_cast(u32x2, b1); img[2] = __builtin_bit_cast(u32x2, b2);
+}
+template <class ASrc>
+__device__ __forceinline__ f32x16 tile_mma_bf16x6(ASrc a, const float* __restrict__ B, int64_t sbk, int64_t sbn, int64_t m0, int n0, int64_t M,
+                                                  int N, int64_t k_begin, int64_t k_end, X6Tile* As, X6Tile* Bs) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave & 1, wn = wave >> 1;
+    f32x16 a00 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, a01 = a00, a11 = a00;
+    const bool a_kfast = a.kfast(), b_kfast = sbk == 1;
+    // this thread's quadruple of A and of B in a K step: k-fast operands 4 threads per row, the others 64 rows per wave (coalesced either way)
+    const int ar = a_kfast ? tid >> 2 : tid & 63, ac = a_kfast ? tid & 3 : tid >> 6;
+    const int br = b_kfast ? tid >> 2 : tid & 63, bc = b_kfast ? tid & 3 : tid >> 6;
+    const bool va = m0 + ar < M, vb = n0 + br < N;
+    a.start4(va, m0 + ar, k_begin + 4 * ac);
+    const float* pb = B + (k_begin + 4 * bc) * sbk + (vb ? (int64_t)(n0 + br) * sbn : 0);
+    const int64_t db_ = GK * sbk;
+    float ra[4], rb[4];
+    auto fetch = [&](int64_t k0) {
+        a.get4(va, m0 + ar, k0 + 4 * ac, k_end, ra);
+        strided_load4(pb, sbk, vb, k0 + 4 * bc, k_end, rb);
+        pb += db_;
+    };
+    auto stash = [&](int buf) {
+        u32x2 ia[3], ib[3];
+        x6_split4(ra, ia);
+        x6_split4(rb, ib);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { As[buf].c[i][ac >> 1][ar][ac & 1] = ia[i]; Bs[buf].c[i][bc >> 1][br][bc & 1] = ib[i]; }
+    };
+    fetch(k_begin);
+    stash(0);
+    __syncthreads();
+    int buf = 0;
+    for (int64_t k0 = k_begin; k0 < k_end; k0 += GK) {
+        const bool more = k0 + GK < k_end;
+        if (more) fetch(k0 + GK);                     // in flight during the MFMAs below
+        bf16x8 x[3], y[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            x[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&As[buf].c[i][lane >> 5][wm * 32 + (lane & 31)][0]));
+            y[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(&Bs[buf].c[i][lane >> 5][wn * 32 + (lane & 31)][0]));
+        }
+        a00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[0], a00, 0, 0, 0);
+        a01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[1], a01, 0, 0, 0);
+        a11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], y[1], a11, 0, 0, 0);
+        a01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], y[0], a01, 0, 0, 0);
+        a11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[2], a11, 0, 0, 0);
+        a11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[2], y[0], a11, 0, 0, 0);
+        if (more) stash(buf ^ 1);                     // the other half: nobody reads it before the barrier
+        __syncthreads();
+        buf ^= 1;
+    }
+    return a00 + (a01 + a11);
+}
+
+// ---- the matrix mode of a kernel: which body its tiles run on, and the LDS tile that body stages through -------------------------------------
+enum { MM_F32 = 0, MM_BF16X6 = 1 };        // GCDM_OPS_MATRIX_F32 / GCDM_OPS_MATRIX_BF16X6
+template <int MODE> struct TileLds { typedef float type[GK][GM + 1]; };
+template <> struct TileLds<MM_BF16X6> { typedef X6Tile type; };
+template <int MODE, class ASrc, class L>
+__device__ __forceinline__ f32x16 tile_body(ASrc a, const float* __restrict__ B, int64_t sbk, int64_t sbn, int64_t m0, int n0, int64_t M, int N,
+                                            int64_t k_begin, int64_t k_end, L* As, L* Bs) {
+    if constexpr (MODE == MM_BF16X6) return tile_mma_bf16x6(a, B, sbk, sbn, m0, n0, M, N, k_begin, k_end, As, Bs);
+    else return tile_mma(a, B, sbk, sbn, m0, n0, M, N, k_begin, k_end, As, Bs);
+}
+// a launch in the mode the C entry read: the fp32 instantiation is the kernel as it always was
+#define GOPS_LAUNCH_MODE(mode, K, ...) \
+    do { if ((mode) == gops::MM_BF16X6) hipLaunchKernelGGL((K<gops::MM_BF16X6>), __VA_ARGS__); else hipLaunchKernelGGL((K<gops::MM_F32>), __VA_ARGS__); } while (0)
+// the same for a kernel whose mode is its second template parameter, behind T1
+#define GOPS_LAUNCH_MODE2(mode, K, T1, ...) \
+    do { if ((mode) == gops::MM_BF16X6) hipLaunchKernelGGL((K<T1, gops::MM_BF16X6>), __VA_ARGS__); else hipLaunchKernelGGL((K<T1, gops::MM_F32>), __VA_ARGS__); } while (0)
+
 // ---- C[M,N] = A[M,K] . B[K,N] (+ bias[N]) ------------------------------------------------------------------------------------------------------
 // General strides, so one kernel serves y = x W^T (A = x, B = W^T), dx = dy W (A = dy, B = W) and dW = dy^T x (A = dy^T, B = x).
 // grid.z = split-K slices writing C + z * M * N (reduced in fixed order by k_reduce_slices: deterministic).
+template <int MODE>
 __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, int64_t sam, int64_t sak, const float* __restrict__ B, int64_t sbk,
                                               int64_t sbn, float* __restrict__ C, const float* __restrict__ bias, int64_t M, int N, int64_t K,
                                               int64_t kslice) {
-    __shared__ float As[2][GK][GM + 1];
-    __shared__ float Bs[2][GK][GN + 1];
+    __shared__ typename TileLds<MODE>::type As[2], Bs[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave & 1, wn = wave >> 1;
     const int64_t m0 = (int64_t)blockIdx.x * GM;
     const int n0 = blockIdx.y * GN;
     const int64_t k_begin = (int64_t)blockIdx.z * kslice, k_end = k_begin + kslice < K ? k_begin + kslice : K;
-    const f32x16 acc = tile_mma(StridedA{A, sam, sak}, B, sbk, sbn, m0, n0, M, N, k_begin, k_end, As, Bs);
+    const f32x16 acc = tile_body<MODE>(StridedA{A, sam, sak}, B, sbk, sbn, m0, n0, M, N, k_begin, k_end, As, Bs);
     float* Cz = C + (int64_t)blockIdx.z * M * N;
     const int col = n0 + wn * 32 + (lane & 31);
     if (col < N) {
@@ -130,10 +264,10 @@ __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, int64
 }
 // the launch: `slices` K slices of a multiple of GK each (trailing ones may be empty: they write 0); 1 slice is the finished product
 static inline void gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, float* C, const float* bias, int64_t M, int N,
-                        int64_t K, hipStream_t st, int slices = 1) {
+                        int64_t K, hipStream_t st, int slices = 1, int mode = MM_F32) {
     const int64_t kslice = ((K + slices - 1) / slices + GK - 1) / GK * GK;
     const dim3 grid((unsigned)((M + GM - 1) / GM), (unsigned)((N + GN - 1) / GN), (unsigned)slices);
-    hipLaunchKernelGGL(k_gemm, grid, dim3(256), 0, st, A, sam, sak, B, sbk, sbn, C, bias, M, N, K, kslice > 0 ? kslice : GK);
+    GOPS_LAUNCH_MODE(mode, k_gemm, grid, dim3(256), 0, st, A, sam, sak, B, sbk, sbn, C, bias, M, N, K, kslice > 0 ? kslice : GK);
 }
 
 __global__ void k_reduce_slices(const float* __restrict__ part, float* __restrict__ out, int64_t n, int slices) {
@@ -171,9 +305,9 @@ static inline int64_t wgrad_offsets(const int64_t* sz, int n, int64_t* off) {
     return t;
 }
 
+template <int MODE>
 __global__ __launch_bounds__(256) void k_wgrad_grouped(WgTable T, float* __restrict__ part) {
-    __shared__ float As[2][GK][GM + 1];
-    __shared__ float Bs[2][GK][GN + 1];
+    __shared__ typename TileLds<MODE>::type As[2], Bs[2];
     int gi = 0;
     while (gi + 1 < T.n && T.g[gi + 1].tile0 <= (int)blockIdx.x) ++gi;
     const WgDesc& D = T.g[gi];
@@ -184,7 +318,7 @@ __global__ __launch_bounds__(256) void k_wgrad_grouped(WgTable T, float* __restr
     const int n0 = (t % tn_count) * GN;
     const int64_t kslice = ((D.K + WG_SLICES - 1) / WG_SLICES + GK - 1) / GK * GK;
     const int64_t k_begin = (int64_t)blockIdx.z * kslice, k_end = k_begin + kslice < D.K ? k_begin + kslice : D.K;
-    const f32x16 acc = tile_mma(StridedA{D.A, D.sam, D.sak}, D.B, D.sbk, D.sbn, m0, n0, D.M, D.N, k_begin, k_end, As, Bs);
+    const f32x16 acc = tile_body<MODE>(StridedA{D.A, D.sam, D.sak}, D.B, D.sbk, D.sbn, m0, n0, D.M, D.N, k_begin, k_end, As, Bs);
     float* Cz = part + (int64_t)blockIdx.z * T.total + D.off;
     const int col = n0 + wn * 32 + (lane & 31);
     if (col < D.N) {
@@ -196,8 +330,8 @@ __global__ __launch_bounds__(256) void k_wgrad_grouped(WgTable T, float* __restr
     }
 }
 // dweights[T.total] = the groups of T, through part[WG_SLICES][T.total]
-static inline void wgrad_launch(const WgTable& T, float* part, float* dweights, hipStream_t st) {
-    hipLaunchKernelGGL(k_wgrad_grouped, dim3((unsigned)T.tiles, 1, WG_SLICES), dim3(256), 0, st, T, part);
+static inline void wgrad_launch(const WgTable& T, float* part, float* dweights, hipStream_t st, int mode = MM_F32) {
+    GOPS_LAUNCH_MODE(mode, k_wgrad_grouped, dim3((unsigned)T.tiles, 1, WG_SLICES), dim3(256), 0, st, T, part);
     hipLaunchKernelGGL(k_reduce_slices, dim3((unsigned)((T.total + 255) / 256)), dim3(256), 0, st, (const float*)part, dweights, T.total, (int)WG_SLICES);
 }
 

@@ -8,6 +8,7 @@ training objective differentiable.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional, Tuple
 
@@ -25,6 +26,34 @@ def _lib():
 def _chk(status: int, what: str) -> None:
     if status != 0:
         raise _native.NativeError(f"{what} failed with status {status} (libgcdm_ops.so)")
+
+
+def set_matrix_mode(mode: str) -> None:
+    """Chooses the matrix instruction under every training GEMM of libgcdm_ops.so (include/gcdm_matrix_mode.h): ``"f32"``, the default, is
+    exact fp32 MFMA; ``"bf16x6"`` is the six-product bf16 split (fp32-class accuracy, not fp32's bits, no range guard).  The switch is
+    process-wide, not per thread, and each operator call reads it once when it is made: linear(), message_layer() and the fused GCP2, forward
+    and backward, and nothing else."""
+    if mode not in _native.MATRIX_MODES:
+        raise ValueError(f"matrix mode must be one of {sorted(_native.MATRIX_MODES)}, got {mode!r}")
+    _chk(_lib().gcdm_ops_set_matrix_mode(_native.MATRIX_MODES[mode]), "gcdm_ops_set_matrix_mode")
+
+
+def get_matrix_mode() -> str:
+    code = int(_lib().gcdm_ops_get_matrix_mode())
+    return next(name for name, c in _native.MATRIX_MODES.items() if c == code)
+
+
+@contextlib.contextmanager
+def matrix_mode(mode: str):
+    """``with ops.matrix_mode("bf16x6"):`` runs the block in that mode and restores the previous one on any exit.  A backward pass called
+    after the block has exited runs in the mode current at that moment, not in the one its forward ran in: keep ``loss.backward()`` inside
+    the block (or use set_matrix_mode) when the gradients are meant to run in it."""
+    previous = get_matrix_mode()
+    set_matrix_mode(mode)
+    try:
+        yield
+    finally:
+        set_matrix_mode(previous)
 
 
 def _dev(t: torch.Tensor) -> None:

@@ -1,6 +1,6 @@
 """Where a training step of the module path spends its time (GPU box): wall clock per step against the GPU-side kernel time of the same steps.
 
-    python tools/train_step_probe.py [steps] [--message-path operators|fused] [--node-path operators|fused]   -> wall ms / step, host enqueue ms / step, HIP-event ms / step
+    python tools/train_step_probe.py [steps] [--message-path operators|fused] [--node-path operators|fused] [--matrix-mode f32|bf16x6]   -> wall ms / step, host enqueue ms / step, HIP-event ms / step
     rocprofv3 --kernel-trace --stats -- python tools/train_step_probe.py 5      (sum of kernel durations / steps = GPU busy time per step)
 
 --update torch|fused adds the update after backward(): `torch` the reference's recipe in stock torch (adaptive clipping with two host
@@ -14,6 +14,9 @@ one autograd node on the fused GCP2 kernels (GCPNetDynamics.set_node_path, inclu
 
 --objective-path fused runs everything around the network evaluation -- noising, loss terms, their backward -- on the fused objective
 (EquivariantVariationalDiffusion.set_objective_path, include/gcdm_objective.h): four launches forward, one backward; independent of the others.
+
+--matrix-mode bf16x6 runs every training GEMM (the plain GEMM, the grouped weight gradients, the fused GCP2's GEMM kernels) on the six-product
+bf16 split instead of fp32 MFMA (ops.set_matrix_mode, include/gcdm_matrix_mode.h); the default f32 is what bench.py times.
 
 The step is bench.py's `training_step`: forward in training mode + loss + backward of one 64-molecule QM9 batch through libgcdm_ops.so's operators."""
 import importlib
@@ -107,9 +110,11 @@ def main():
     ap.add_argument("--node-path", choices=("operators", "fused"), default="operators")
     ap.add_argument("--objective-path", choices=("operators", "fused"), default="operators")
     ap.add_argument("--update", choices=("none", "torch", "fused"), default="none")
+    ap.add_argument("--matrix-mode", choices=("f32", "bf16x6"), default="f32")
     args = ap.parse_args()
     steps = args.steps
     once, dev = build_step(args.message_path, args.update, args.node_path, args.objective_path)
+    importlib.import_module("bio-diffusion_amd").ops.set_matrix_mode(args.matrix_mode)
     for _ in range(3):
         once()
     torch.cuda.synchronize(dev)
@@ -122,7 +127,7 @@ def main():
     t_host = (time.perf_counter() - t0) / steps * 1e3          # host done enqueueing
     torch.cuda.synchronize(dev)
     wall = (time.perf_counter() - t0) / steps * 1e3
-    print(f"training step, 64 x 19, message path {args.message_path}, node path {args.node_path}, objective path {args.objective_path}, update {args.update}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
+    print(f"training step, 64 x 19, message path {args.message_path}, node path {args.node_path}, objective path {args.objective_path}, update {args.update}, matrix mode {args.matrix_mode}: wall {wall:.2f} ms / step, host enqueue {t_host:.2f} ms / step, HIP events {ev[0].elapsed_time(ev[1]) / steps:.2f} ms / step")
 
 
 if __name__ == "__main__":
