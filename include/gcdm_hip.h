@@ -136,6 +136,14 @@ int gcdm_sample_final(gcdm_handle* h, const float* z0, const float* context, con
 int gcdm_forward_sc(gcdm_handle* h, const float* xh, const float* xh_self_cond, const float* t, const float* context, float* out,
                     uint32_t* flags, void* stream);
 
+/* On-device noise (every `noise == NULL` above and below).  Entry (node, col) of draw number `draw` under `seed` is a standard normal from
+ * Philox4x32-10 (Salmon et al., SC'11; the Random123 constants) with counter {node, draw, col >> 1, 0x6c078965} and key {seed low 32 bits, seed high 32 bits}:
+ * u1, u2 = ((w >> 8) + 0.5) * 2^-24 of output words 0 and 1, evaluated in fp32; r = sqrt(-2 ln u1); even col = r cos(2 pi u2), odd col = r sin(2 pi u2).
+ * `node` is the row's index in the flat batch plus the option "node_base" (packed plan: its index within its sub-batch, seed = that sub-batch's).
+ * Draw numbers: gcdm_sample_init 0x7fffffff; gcdm_sample_final[_sc] 0x7ffffffe; the step at s_index (gcdm_sample_step / _step_to, and the first transition of
+ * gcdm_sample_step_sc) s_index; the self-conditioning estimate of gcdm_sample_step_sc 0x20000000 | s_index; gcdm_inpaint_step draw_base (known part), draw_base + 1
+ * (model step), draw_base + 2 (self-conditioning estimate); gcdm_inpaint_jump its `draw` argument. */
+
 /* Draws z_T (variational_diffusion.py:795-819) into z [N,3+F] from `noise` (device) or Philox(seed). */
 int gcdm_sample_init(gcdm_handle* h, float* z, const float* noise, uint64_t seed, void* stream);
 
