@@ -7,6 +7,7 @@
 #include "gcdm_layer_x3.hip.h"
 #include "gcdm_embed_x3.hip.h"
 #include "gcdm_stability.hip.h"
+#include "gcdm_plan.h"
 #include "../../include/gcdm_hip.h"
 
 #include <cmath>
@@ -20,9 +21,33 @@
 
 namespace {
 
-struct DevBuf {
-    void* p = nullptr;
+static_assert(PLAN_S == GCDM_S && PLAN_AGGW == GCDM_AGGW, "gcdm_plan.h sizes the workspace with the kernels' constants");
+
+// One device allocation, freed with its owner (whoever destroys or assigns over it holds the DeviceGuard).  Reads as the pointer it holds.
+template <class T>
+struct DevMem {
+    T* p = nullptr;
     size_t bytes = 0;
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevMem& operator=(DevMem&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }      // (o frees what this held)
+    ~DevMem() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t count) {
+        *this = DevMem{};
+        const hipError_t e = hipMalloc(&p, count * sizeof(T));
+        if (e == hipSuccess) bytes = count * sizeof(T);
+        else p = nullptr;
+        return e;
+    }
+    hipError_t alloc_zeroed(size_t count) {
+        const hipError_t e = alloc(count);
+        return e != hipSuccess ? e : hipMemset(p, 0, bytes);
+    }
+    hipError_t upload(const std::vector<T>& v) {
+        const hipError_t e = alloc(v.size());
+        return e != hipSuccess ? e : hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice);
+    }
+    operator T*() const { return p; }
 };
 
 // The node-level halves of a layer's msg0, which the node stage in front of it (the previous layer's, or the embedding's) computes
@@ -52,6 +77,26 @@ struct ModelDev {
     const h8 *ee_xwH = nullptr, *ee_xwL = nullptr, *ee_xgH = nullptr, *ee_xgL = nullptr;
 };
 
+// A batch plan on the device: the tables of a PlanHost (gcdm_plan.h) and the workspace.  plan_impl builds one beside the handle's and moves it in, so the
+// handle holds a whole plan or none (N == 0); assigning Plan{} over it frees everything.
+struct Plan : PlanScalars {
+    DevMem<int> d_noff, d_erow, d_ecol, d_ncnt, d_rowstart;
+    DevMem<float> d_mask;            // 1 / 0 per node when the plan has masked nodes (gcdm_plan_batch_masked), else null
+    DevMem<float> ws;                // workspace pool, zeroed at plan time; its sub-buffers (an empty one is null):
+#define GCDM_WS_MEMBER(id, name, floats) float* id = nullptr;
+    GCDM_WS_BUFFERS(GCDM_WS_MEMBER)
+#undef GCDM_WS_MEMBER
+    // Fused layer launch (gcdm_layer_x3.hip.h): the node-tile queue table (PlanHost::tail_tab; null when the plan does not qualify) and its counters --
+    // ready[tail_tiles32] | qcur[TAIL_CTR_WORDS = 25]: queue cursors [0..7], workgroups that left [8], xcc_seen [9..16], arrivals [17..24]
+    // (zeroed at plan time, self-resetting; TailArgs::ready / qcur)
+    DevMem<int> d_tail_tab, d_tail_ctr;
+    // packed plan (K > 0; else null and every kernel takes its usual path)
+    DevMem<int> d_mol_sub, d_sub_noff, d_tvalid;
+    DevMem<uint64_t> d_seeds;
+    DevMem<uint32_t> d_sub_flags;
+    PackTab pack() const { return PackTab{d_mol_sub, d_sub_noff, d_seeds, d_sub_flags}; }
+};
+
 }  // namespace
 
 struct gcdm_handle {
@@ -62,42 +107,18 @@ struct gcdm_handle {
     // derived dims
     int F = 0, C = 0, Fin = 0, FinG = 0, D = 0, Se = 0, Ve = 0, L = 0, H0 = 0;
     int sc = 0, FinP = 0;            // self-conditioning: Fin = [h | h_sc | t | ctx] feeds the node embedding, FinP = F + 1 + C is what the projection returns
-    float *X0SC = nullptr, *BL = nullptr, *USC = nullptr;
+    PlanDims dims() const { PlanDims d; d.D = D; d.FinG = FinG; d.Se = Se; d.Ve = Ve; d.H0 = H0; d.sc = sc; d.cus = cus; return d; }
     // device weights
-    float* wpool = nullptr;
-    size_t wpool_bytes = 0;
+    DevMem<float> wpool;
     ModelDev m;                      // pointers into wpool
     std::vector<float> gamma;
-    // plan
-    int B = 0, N = 0, max_n = 0;
-    int64_t E = 0;
-    int *d_noff = nullptr, *d_erow = nullptr, *d_ecol = nullptr, *d_ncnt = nullptr, *d_rowstart = nullptr;
-    float* d_mask = nullptr;         // 1 / 0 per node when the plan has masked nodes (gcdm_plan_batch_masked), else null
-    float* ws = nullptr;  // workspace pool
-    size_t ws_floats = 0;
-    float *X0 = nullptr, *XC = nullptr, *FBAR = nullptr, *CHI0 = nullptr, *HIN4 = nullptr, *H4 = nullptr, *CHI = nullptr, *PQ4 = nullptr,
-          *VDI = nullptr, *VDJ = nullptr, *AGG = nullptr, *PART = nullptr, *VEL = nullptr, *EPS = nullptr, *EP4 = nullptr, *AL = nullptr, *U = nullptr, *FR = nullptr, *PROF = nullptr, *ZK = nullptr, *ZU = nullptr, *ZROW = nullptr;
-    float *PQ4b = nullptr, *VDIb = nullptr, *VDJb = nullptr;   // second set of the node-level msg0 halves: layer l gathers set l & 1, its node tiles write set (l + 1) & 1 (round 6:
-                                                               // with the node tiles as a tail role of the edge workgroups both happen in ONE launch)
-    // Fused layer launch (gcdm_layer_x3.hip.h): table of the node-tile queue (TailArgs::tab; null when the plan does not qualify) and its counters
-    int* d_tail_tab = nullptr;                     // XCD x [8 x + 0..3]: first owned node tile, owned node tiles, edge tiles + owned node tiles (not read), rel_node_end |
-                                                   // [64 + t]: edge tiles node tile t waits for, | 1 << 16 when they reach into the next XCD's range (TailArgs::tab)
-    int* d_tail_ctr = nullptr;                     // ready[tail_tiles32] | qcur[TAIL_CTR_WORDS = 25]: queue cursors [0..7], workgroups that left [8], xcc_seen [9..16],
-                                                   // arrivals [17..24]  (zeroed at plan time, self-resetting; TailArgs::ready / qcur)
-    int tail_tiles32 = 0;
+    Plan plan;                       // the batch plan, whole or none
+    bool planned() const { return plan.N != 0; }
     int fuse_node = 1;               // option "fuse_node" / env GCDM_FUSE_NODE: 1 = the layer's node tiles run as a tail role of the persistent edge workgroups (one launch
                                      // per layer) where the plan qualifies; 0 = two launches per layer (rounds 1-5)
     int fuse_active = 0;             // option "fuse_active" (read-only): the last forward used the fused launch
-    uint32_t* d_flags = nullptr;        // FlagBlock (gcdm_kernels.hip.h): plan-wide flag word, statistics of gcdm_encode_samples, the packed plan's tables for the NaN sites
-    float* d_gmean = nullptr;
-    // packed plan (gcdm_plan_batches): K sub-batches end to end; K = 0: an ordinary plan, the tables are null and every kernel takes its usual path
-    int K = 0;
-    int *d_mol_sub = nullptr, *d_sub_noff = nullptr;
-    uint64_t* d_seeds = nullptr;
-    uint32_t* d_sub_flags = nullptr;
-    int* d_tvalid = nullptr;            // real edges of every 64-group of the (padded) edge list: a sub-batch's edges start on a 64-edge boundary
-    int64_t E_real = 0;                 // edges without that padding (E counts the slots of the list)
-    PackTab pack() const { return PackTab{d_mol_sub, d_sub_noff, d_seeds, d_sub_flags}; }
+    DevMem<uint32_t> d_flags;        // FlagBlock (gcdm_kernels.hip.h): plan-wide flag word, statistics of gcdm_encode_samples, the packed plan's tables for the NaN sites
+    DevMem<float> d_gmean;
     int flat_prev = 0, flat_next = 0;   // the plan is a slice of a larger flat batch (options "flat_prev" / "flat_next"; include/gcdm_hip.h)
     uint32_t node_base = 0;             // option "node_base": flat index of the slice's first node (Philox counter)
     int fix_noise = 0;                  // option "fix_noise": x-noise centred over the whole flat batch (mol_gen_sample(fix_noise=True))
@@ -141,8 +162,8 @@ struct gcdm_handle {
     hipStream_t cap_stream = nullptr;  // capture happens here (the caller's stream may be the null stream, which cannot capture)
     hipEvent_t sg_done = nullptr; bool sg_inflight = false;   // recorded behind every graph launch: an exec (and the row table it reads) is retired only after it
     hipStream_t sg_last_stream = nullptr;                      // ... and a launch on ANOTHER stream first waits for it, so that the one event covers every launch in flight
-    StepRow* d_rows = nullptr; int rows_steps = 0;
-    int* d_cursor = nullptr; int cursor_expected = -1;
+    DevMem<StepRow> d_rows; int rows_steps = 0;
+    DevMem<int> d_cursor; int cursor_expected = -1;
     int64_t graph_launches = 0;        // option "graph_launches" (read-only): steps served by the graph since the handle was created
 };
 
@@ -465,34 +486,14 @@ bool build_gcp(gcdm_handle* h, Pool& pool, const std::string& pre, int s_in, int
     return true;
 }
 
-void free_plan(gcdm_handle* h) {
-    if (h->d_noff) (void)hipFree(h->d_noff);
-    if (h->d_erow) (void)hipFree(h->d_erow);
-    if (h->d_ecol) (void)hipFree(h->d_ecol);
-    if (h->d_ncnt) (void)hipFree(h->d_ncnt);
-    if (h->d_rowstart) (void)hipFree(h->d_rowstart);
-    if (h->d_mask) (void)hipFree(h->d_mask);
-    h->d_mask = nullptr;
-    if (h->d_tail_tab) (void)hipFree(h->d_tail_tab);
-    h->d_tail_tab = nullptr;
-    if (h->d_tail_ctr) (void)hipFree(h->d_tail_ctr);
-    h->d_tail_ctr = nullptr;
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->K) {
-        if (h->d_flags) (void)hipMemset(reinterpret_cast<char*>(h->d_flags) + offsetof(FlagBlock, num_sub), 0, sizeof(FlagBlock) - offsetof(FlagBlock, num_sub));
-        if (h->d_mol_sub) (void)hipFree(h->d_mol_sub);
-        if (h->d_sub_noff) (void)hipFree(h->d_sub_noff);
-        if (h->d_seeds) (void)hipFree(h->d_seeds);
-        if (h->d_sub_flags) (void)hipFree(h->d_sub_flags);
-        if (h->d_tvalid) (void)hipFree(h->d_tvalid);
-        h->d_tvalid = nullptr;
-        h->d_mol_sub = h->d_sub_noff = nullptr; h->d_seeds = nullptr; h->d_sub_flags = nullptr;
-        h->K = 0;
-    }
-    h->d_noff = h->d_erow = h->d_ecol = h->d_ncnt = h->d_rowstart = nullptr;
-    h->ws = nullptr;
-    h->B = h->N = 0;
-    h->E = 0;
+// The checks the sampler entry points share; `who` is the entry's name in the message
+int need_gamma(gcdm_handle* h, const char* who) {
+    if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, std::string(who) + ": gamma table not set");
+    return 0;
+}
+int need_unmasked(gcdm_handle* h) {
+    if (h->plan.d_mask) return fail(h, "the sampler entry points need an all-True node mask (plan with gcdm_plan_batch); masked plans serve gcdm_forward only");
+    return 0;
 }
 
 // ---- kernel table: which instantiation serves (Se, tile, role), with its launch geometry ---------
@@ -594,9 +595,9 @@ int record_event(const Eval& ev, int l, LayerEvent what) {
 void embed_edges(const Eval& ev) {
     gcdm_handle* h = ev.h;
     const ModelDev& m = h->m;
-    EdgeEmbedArgs ea{h->X0, h->XC, ev.N, h->d_erow, h->d_ecol, ev.E, m.ee_ws, m.ee_bs, m.ee_wd, m.ee_wdf, m.ee_kappa, m.ee_wg, m.ee_bg,
-                     (v4f*)h->EP4, h->AL, h->U, h->FR,
-                     h->sc, (h->sc ? 2 : 1) + h->Ve + 9, h->X0SC, m.ee_wd1, m.ee_wdf1, m.ee_kappa1, h->BL, h->USC};
+    EdgeEmbedArgs ea{h->plan.X0, h->plan.XC, ev.N, h->plan.d_erow, h->plan.d_ecol, ev.E, m.ee_ws, m.ee_bs, m.ee_wd, m.ee_wdf, m.ee_kappa, m.ee_wg, m.ee_bg,
+                     (v4f*)h->plan.EP4, h->plan.AL, h->plan.U, h->plan.FR,
+                     h->sc, (h->sc ? 2 : 1) + h->Ve + 9, h->plan.X0SC, m.ee_wd1, m.ee_wdf1, m.ee_kappa1, h->plan.BL, h->plan.USC};
     if (h->use_x3()) {
         const auto k = edge_embed_x3_kernel(h->Se);
         launch(k, (ev.E + k.tile - 1) / k.tile, ev.st, EdgeEmbedX3Args{h->x3c(), ea, m.ee_xwH, m.ee_xwL, m.ee_xgH, m.ee_xgL});
@@ -612,7 +613,7 @@ NodeArgs node_args(const Eval& ev, int l) {
     const gcdm_handle* h = ev.h;
     NodeArgs na = ev.node;
     const bool setb = ((l + 1) & 1) != 0;
-    na.PQ4 = (v4f*)(setb ? h->PQ4b : h->PQ4); na.VDI = setb ? h->VDIb : h->VDI; na.VDJ = setb ? h->VDJb : h->VDJ;
+    na.PQ4 = (v4f*)(setb ? h->plan.PQ4b : h->plan.PQ4); na.VDI = setb ? h->plan.VDIb : h->plan.VDI; na.VDJ = setb ? h->plan.VDJb : h->plan.VDJ;
     if (l >= 0) {
         na.agg.tile_shift = ev.ET == 32 ? 5 : 6;
         na.ff = h->m.layers[l].ff; na.pos = h->m.layers[l].pos;
@@ -634,7 +635,7 @@ int node_x3_args(const Eval& ev, int l, NodeX3Args& nx) {
     if (l >= 0) { nx.ff = h->m.layers[l].ffx; nx.pos = h->m.layers[l].posx; }
     if ((l >= 0 && (nx.ff.KB != 34 || nx.pos.KB != 18)) || nx.proj.KB != 19)      // compile-time k-block counts of k_node_x3
         return fail(h, "internal: node k-block counts differ from the kernel's compile-time constants");
-    nx.prof = (h->profile_node && l >= 0 && l + 1 < h->L) ? h->PROF : nullptr;
+    nx.prof = (h->profile_node && l >= 0 && l + 1 < h->L) ? h->plan.PROF : nullptr;
     const NextMsg0& nm = h->m.layers[std::min(l + 1, h->L - 1)].next;
     nx.wpqH = nm.wpqH; nx.wpqL = nm.wpqL; nx.vdH = nm.vdH; nx.vdL = nm.vdL; nx.bpqx = nm.bpqx;
     return 0;
@@ -661,15 +662,15 @@ EdgeMsgX3Args edge_args(const Eval& ev, int l) {
     const gcdm_handle* h = ev.h;
     EdgeMsgX3Args xa = h->m.layers[l].edge;
     EdgeMsgArgs& ma = xa.base;
-    ma.EP4 = (const v4f*)h->EP4; ma.AL = h->AL; ma.U = h->U; ma.FR = h->FR; ma.EROW = h->d_erow; ma.ECOL = h->d_ecol; ma.NCNT = h->d_ncnt;
-    ma.BL = h->BL; ma.USC = h->USC;
+    ma.EP4 = (const v4f*)h->plan.EP4; ma.AL = h->plan.AL; ma.U = h->plan.U; ma.FR = h->plan.FR; ma.EROW = h->plan.d_erow; ma.ECOL = h->plan.d_ecol; ma.NCNT = h->plan.d_ncnt;
+    ma.BL = h->plan.BL; ma.USC = h->plan.USC;
     const bool odd = (l & 1) != 0;          // the set of node-level msg0 halves this layer gathers
-    ma.E = ev.E; ma.N = ev.N; ma.PQ4 = (const v4f*)(odd ? h->PQ4b : h->PQ4); ma.VDI = odd ? h->VDIb : h->VDI; ma.VDJ = odd ? h->VDJb : h->VDJ; ma.AGG = h->AGG; ma.PART = h->PART;
-    ma.prof = h->profile_phases ? h->PROF : nullptr;
-    ma.TVALID = h->d_tvalid;
+    ma.E = ev.E; ma.N = ev.N; ma.PQ4 = (const v4f*)(odd ? h->plan.PQ4b : h->plan.PQ4); ma.VDI = odd ? h->plan.VDIb : h->plan.VDI; ma.VDJ = odd ? h->plan.VDJb : h->plan.VDJ; ma.AGG = h->plan.AGG; ma.PART = h->plan.PART;
+    ma.prof = h->profile_phases ? h->plan.PROF : nullptr;
+    ma.TVALID = h->plan.d_tvalid;
     xa.x3c = h->x3c();
-    xa.wpool = h->wpool; xa.wpool_bytes = (uint32_t)h->wpool_bytes;
-    xa.wspool = h->ws; xa.wspool_bytes = (uint32_t)(h->ws_floats * sizeof(float));
+    xa.wpool = h->wpool; xa.wpool_bytes = (uint32_t)h->wpool.bytes;
+    xa.wspool = h->plan.ws; xa.wspool_bytes = (uint32_t)h->plan.ws.bytes;
     xa.flags_dev = h->d_flags;
     return xa;
 }
@@ -687,7 +688,7 @@ int layer_fused(const Eval& ev, int l, const EdgeMsgX3Args& xa, int wgs) {
     gcdm_handle* h = ev.h;
     TailArgs ta{};
     if (node_x3_args(ev, l, ta.nx)) return -1;
-    ta.ready = h->d_tail_ctr; ta.qcur = h->d_tail_ctr + h->tail_tiles32; ta.tab = h->d_tail_tab;
+    ta.ready = h->plan.d_tail_ctr; ta.qcur = h->plan.d_tail_ctr + h->plan.tail_tiles32; ta.tab = h->plan.d_tail_tab;
     ta.num_wgs = wgs;
     launch(edge_x3_kernel<NodeTailRole<32>>(h->Se, ev.ET), wgs, ev.st, NodeTailRole<32>::Args{xa, ta});
     return record_event(ev, l, EDGE_END);
@@ -713,9 +714,9 @@ int layer_x3(const Eval& ev, int l) {
     const bool persistent = !(h->persistent == 0 || ev.tiles <= wgs || wgs < 8);
     if (!persistent) wgs = ev.tiles;
     xa.wg_stride = persistent ? wgs / 8 : ev.tiles;
-    h->fuse_active = ev.ET == 64 && persistent && h->fuse_node && !h->profile_node && !h->d_mask && h->d_tail_ctr && h->d_tail_tab;
+    h->fuse_active = ev.ET == 64 && persistent && h->fuse_node && !h->profile_node && !h->plan.d_mask && h->plan.d_tail_ctr && h->plan.d_tail_tab;
     if (h->fuse_active) return layer_fused(ev, l, xa, wgs);
-    return h->K ? layer_x3_split<PackedRole>(ev, l, xa, wgs) : layer_x3_split<NoTailRole>(ev, l, xa, wgs);
+    return h->plan.K ? layer_x3_split<PackedRole>(ev, l, xa, wgs) : layer_x3_split<NoTailRole>(ev, l, xa, wgs);
 }
 
 int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, const float* t, const StepFeed* feed, const float* context, float* out,
@@ -723,29 +724,29 @@ int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, const floa
     if (!h) return -1;
     if (xh_sc && !h->sc) return fail(h, "gcdm_forward_sc: the handle was created without self_condition");
     if (!h->finalized) return fail(h, "gcdm_forward: weights not finalized");
-    if (!h->N) return fail(h, "gcdm_forward: no batch plan");
+    if (!h->planned()) return fail(h, "gcdm_forward: no batch plan");
     if (!xh || !out) return fail(h, "gcdm_forward: null tensor");
     if (h->C && !context) return fail(h, "gcdm_forward: context required");
     DeviceGuard guard(h->cfg.device);
     Eval ev{};
-    ev.h = h; ev.st = (hipStream_t)stream_; ev.N = h->N; ev.E = (int)h->E;
+    ev.h = h; ev.st = (hipStream_t)stream_; ev.N = h->plan.N; ev.E = (int)h->plan.E;
     ev.ET = h->tile(); ev.tiles = (ev.E + ev.ET - 1) / ev.ET;
-    const int N = ev.N, B = h->B;
+    const int N = ev.N, B = h->plan.B;
     h->fuse_active = 0;
-    PrepArgs pa{xh, t, context, h->d_noff, N, h->F, h->C, h->FinG, h->X0, h->XC, h->FBAR, h->CHI0, (v4f*)h->HIN4, h->flat_prev, h->flat_next,
-                h->sc, xh_sc, h->X0SC, h->d_mask};
+    PrepArgs pa{xh, t, context, h->plan.d_noff, N, h->F, h->C, h->FinG, h->plan.X0, h->plan.XC, h->plan.FBAR, h->plan.CHI0, (v4f*)h->plan.HIN4, h->flat_prev, h->flat_next,
+                h->sc, xh_sc, h->plan.X0SC, h->plan.d_mask};
     if (feed) { pa.t = nullptr; pa.t_rows = feed->rows; pa.t_cursor = feed->cursor; pa.t_value = feed->t_value; }
     pa.flags_dev = h->d_flags;            // cleared by the first kernel of the evaluation
-    pa.pack = h->pack();
-    hipLaunchKernelGGL(k_prep, dim3(B), dim3(64), 3 * h->max_n * sizeof(float), ev.st, pa);
+    pa.pack = h->plan.pack();
+    hipLaunchKernelGGL(k_prep, dim3(B), dim3(64), 3 * h->plan.max_n * sizeof(float), ev.st, pa);
     embed_edges(ev);
 
     NodeArgs& na = ev.node;
     na.N = N; na.F = h->F; na.C = h->C; na.FinG = h->FinG; na.Dout = h->D; na.pos_weight = h->cfg.node_positions_weight;
-    na.HIN4 = (const v4f*)h->HIN4; na.CHI0 = h->CHI0; na.emb = h->m.emb;
-    na.agg = AggSrc{h->AGG, h->PART, h->d_rowstart, h->d_ncnt, 0, h->ZROW}; na.H4 = (v4f*)h->H4; na.CHI = h->CHI; na.XC = h->XC; na.X0 = h->X0; na.FBAR = h->FBAR;
+    na.HIN4 = (const v4f*)h->plan.HIN4; na.CHI0 = h->plan.CHI0; na.emb = h->m.emb;
+    na.agg = AggSrc{h->plan.AGG, h->plan.PART, h->plan.d_rowstart, h->plan.d_ncnt, 0, h->plan.ZROW}; na.H4 = (v4f*)h->plan.H4; na.CHI = h->plan.CHI; na.XC = h->plan.XC; na.X0 = h->plan.X0; na.FBAR = h->plan.FBAR;
     na.H0 = h->H0;
-    na.proj = h->m.proj; na.OUT = out; na.VEL = h->VEL; na.flags_dev = h->d_flags; na.mask = h->d_mask;
+    na.proj = h->m.proj; na.OUT = out; na.VEL = h->plan.VEL; na.flags_dev = h->d_flags; na.mask = h->plan.d_mask;
     if (node_stage(ev, -1)) return -1;          // node embedding; writes set 0 of the msg0 halves for layer 0
 
     const int L = (h->layer_limit >= 0 && h->layer_limit < h->L) ? h->layer_limit : h->L;
@@ -755,7 +756,7 @@ int forward_impl(gcdm_handle* h, const float* xh, const float* xh_sc, const floa
         if (record_event(ev, l, NODE_END)) return -1;          // end of the layer's node kernel (gcdm_profile_node_kernel_ms)
     }
     if (L == h->L && !feed) {               // (the sampler's evaluations: inside their k_sample launch)
-        FinishArgs fa{h->VEL, h->d_noff, N, h->D, out, h->d_flags, flags, h->d_mask, h->pack()};
+        FinishArgs fa{h->plan.VEL, h->plan.d_noff, N, h->D, out, h->d_flags, flags, h->plan.d_mask, h->plan.pack()};
         hipLaunchKernelGGL(k_finish, dim3(B), dim3(64), 0, ev.st, fa);
     }
     HIP_OK(h, hipGetLastError());
@@ -804,25 +805,18 @@ int gcdm_create(const GcdmConfig* cfg, gcdm_handle** out) {
         int n = 0;
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && n > 0) h->cus = n;
     }
-    HIP_OK(h, hipMalloc(&h->d_flags, sizeof(FlagBlock)));               // [0] flag word, [1..2] statistics of gcdm_encode_samples, then the packed plan's tables
-    HIP_OK(h, hipMemset(h->d_flags, 0, sizeof(FlagBlock)));
+    HIP_OK(h, h->d_flags.alloc_zeroed(sizeof(FlagBlock) / sizeof(uint32_t)));      // [0] flag word, [1..2] statistics of gcdm_encode_samples, then the packed plan's tables
     return 0;
 }
 
 int gcdm_destroy(gcdm_handle* h) {
     if (!h) return 0;
     DeviceGuard guard(h->cfg.device);
-    free_plan(h);
     for (auto& e : h->ev) (void)hipEventDestroy(e);
-    if (h->wpool) (void)hipFree(h->wpool);
-    if (h->d_flags) (void)hipFree(h->d_flags);
-    if (h->d_gmean) (void)hipFree(h->d_gmean);
-    drop_step_graph(h);
-    if (h->d_rows) (void)hipFree(h->d_rows);
-    if (h->d_cursor) (void)hipFree(h->d_cursor);
+    drop_step_graph(h);               // (waits for a graph in flight: it reads the plan and the row table)
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     if (h->sg_done) (void)hipEventDestroy(h->sg_done);
-    delete h;
+    delete h;                         // the plan, the weight pool and the other device memory go with their members
     return 0;
 }
 
@@ -1054,16 +1048,12 @@ static int finalize_pass(gcdm_handle* h, int k_shift) {
     pool.host.resize(pool.host.size() + (size_t)X3_TAIL_BLOCKS * 64 * 4 * 2, 0.f);   // un-clamped weight prefetch of the last packed array
     const size_t bytes = pool.host.size() * sizeof(float);
     if (bytes >= ((size_t)1 << 32)) return fail(h, "gcdm_finalize_weights: weight pool exceeds 4 GB");
-    float* dev = nullptr;
-    HIP_OK(h, hipMalloc(&dev, bytes));
-    if (hipError_t e = hipMemcpy(dev, pool.host.data(), bytes, hipMemcpyHostToDevice)) {
-        (void)hipFree(dev);
+    DevMem<float> dev;
+    HIP_OK(h, dev.alloc(pool.host.size()));
+    if (hipError_t e = hipMemcpy(dev, pool.host.data(), bytes, hipMemcpyHostToDevice))
         return fail(h, std::string("hipMemcpy(weight pool): ") + hipGetErrorString(e));
-    }
     pool.resolve(dev);
-    if (h->wpool) (void)hipFree(h->wpool);
-    h->wpool = dev;
-    h->wpool_bytes = bytes;
+    h->wpool = std::move(dev);        // (frees the pool it replaces)
     h->m = std::move(m);              // (the layer vector keeps its storage; the other slots are patched already)
     h->x3_shift = k_shift;
     if (!h->attr_set) {
@@ -1103,7 +1093,7 @@ static int plan_impl(gcdm_handle* h, int32_t B, const int32_t* nn, const uint8_t
 int gcdm_plan_batch(gcdm_handle* h, int32_t B, const int32_t* nn) { return plan_impl(h, B, nn, nullptr, 0, nullptr); }
 
 int gcdm_plan_batch_masked(gcdm_handle* h, int32_t B, const int32_t* nn, const uint8_t* node_mask) {
-    if (h && h->K && node_mask) return refuse_packed(h, "gcdm_plan_batch_masked");
+    if (h && h->plan.K && node_mask) return refuse_packed(h, "gcdm_plan_batch_masked");
     return plan_impl(h, B, nn, node_mask, 0, nullptr);
 }
 
@@ -1123,12 +1113,48 @@ int gcdm_plan_batches(gcdm_handle* h, int32_t K, const int32_t* mols_per_batch, 
 
 int gcdm_set_batch_seeds(gcdm_handle* h, int32_t K, const uint64_t* host_seeds) {
     if (!h || !host_seeds) return fail(h, "gcdm_set_batch_seeds: bad argument");
-    if (!h->K) return fail(h, "gcdm_set_batch_seeds: the handle has no packed plan (gcdm_plan_batches)");
-    if (K != h->K) return fail(h, "gcdm_set_batch_seeds: num_batches differs from the packed plan's");
+    if (!h->plan.K) return fail(h, "gcdm_set_batch_seeds: the handle has no packed plan (gcdm_plan_batches)");
+    if (K != h->plan.K) return fail(h, "gcdm_set_batch_seeds: num_batches differs from the packed plan's");
     DeviceGuard guard(h->cfg.device);
     // the table keeps its address (a captured step reads it), so nothing that may still read the old seeds is in flight when it changes
     HIP_OK(h, hipDeviceSynchronize());
-    HIP_OK(h, hipMemcpy(h->d_seeds, host_seeds, (size_t)K * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_OK(h, hipMemcpy(h->plan.d_seeds, host_seeds, (size_t)K * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The packed plan's part of the handle's FlagBlock: K and the two tables the NaN sites find their sub-batch's word with (all zero: not packed)
+static hipError_t write_flag_block_pack(gcdm_handle* h, const FlagBlock& fb) {
+    constexpr size_t at = offsetof(FlagBlock, num_sub);
+    return hipMemcpy(reinterpret_cast<char*>(h->d_flags.p) + at, reinterpret_cast<const char*>(&fb) + at, sizeof(FlagBlock) - at, hipMemcpyHostToDevice);
+}
+
+// The device half of a plan, into `p`: the tables, the zeroed workspace (ZROW relies on it) with its sub-buffers, zeroed counters, seeds and sub-batch flag words
+static int upload_plan(gcdm_handle* h, const PlanHost& ph, const WsLayout& wl, Plan& p) {
+    static_cast<PlanScalars&>(p) = ph;
+    if (!ph.mask.empty()) HIP_OK(h, p.d_mask.upload(ph.mask));
+    HIP_OK(h, p.d_noff.upload(ph.noff));
+    HIP_OK(h, p.d_erow.upload(ph.erow));
+    HIP_OK(h, p.d_ecol.upload(ph.ecol));
+    HIP_OK(h, p.d_ncnt.upload(ph.ncnt));
+    HIP_OK(h, p.d_rowstart.upload(ph.rowstart));
+    HIP_OK(h, p.ws.alloc_zeroed(wl.total));
+#define GCDM_WS_RESOLVE(id, name, count) p.id = wl.buf[WS_##id].floats ? p.ws.p + wl.buf[WS_##id].off : nullptr;
+    GCDM_WS_BUFFERS(GCDM_WS_RESOLVE)
+#undef GCDM_WS_RESOLVE
+    if (ph.K > 0) {
+        HIP_OK(h, p.d_mol_sub.upload(ph.mol_sub));
+        HIP_OK(h, p.d_sub_noff.upload(ph.sub_noff));
+        HIP_OK(h, p.d_seeds.alloc_zeroed((size_t)ph.K));
+        HIP_OK(h, p.d_sub_flags.alloc_zeroed((size_t)ph.K));
+        HIP_OK(h, p.d_tvalid.upload(ph.tvalid));
+    }
+    if (!ph.tail_tab.empty()) HIP_OK(h, p.d_tail_tab.upload(ph.tail_tab));
+    if (ph.tail_tiles32) HIP_OK(h, p.d_tail_ctr.alloc_zeroed((size_t)ph.tail_tiles32 + TAIL_CTR_WORDS));
+    if (ph.K > 0) {            // last, when nothing can fail any more: the FlagBlock points into a plan the handle is about to own
+        FlagBlock fb{};
+        fb.num_sub = (uint32_t)ph.K; fb.sub_noff = p.d_sub_noff; fb.sub_flags = p.d_sub_flags;
+        HIP_OK(h, write_flag_block_pack(h, fb));
+    }
     return 0;
 }
 
@@ -1136,166 +1162,17 @@ static int plan_impl(gcdm_handle* h, int32_t B, const int32_t* nn, const uint8_t
     if (!h || B <= 0 || !nn) return fail(h, "gcdm_plan_batch: bad argument");
     DeviceGuard guard(h->cfg.device);
     drop_step_graph(h);
-    std::vector<int> noff(B + 1, 0);
-    int64_t E = 0;
-    int max_n = 0;
-    bool masked = false;
-    // packed plan: first molecule of every sub-batch.  The edges of a sub-batch start on a 64-edge boundary of the flat edge list (the slots up to it repeat the last
-    // edge in front of them and are no part of any row: EdgeMsgArgs::TVALID) -- tile boundaries then cut its rows exactly where they cut them in a plan of its own, which
-    // is what makes its partial row sums (AggSrc), and so its results, those of the single run bit for bit.  64 covers both tile sizes.
-    std::vector<char> sub_first(B, 0);
-    for (int k = 0, b = 0; k < K; b += mols_per_batch[k], ++k) sub_first[b] = 1;
-    for (int b = 0; b < B; ++b) {
-        if (nn[b] <= 0) return fail(h, "gcdm_plan_batch: every molecule needs >= 1 atom");
-        if (sub_first[b]) E = (E + 63) / 64 * 64;
-        noff[b + 1] = noff[b] + nn[b];
-        int64_t m = nn[b];
-        if (node_mask) {            // edges only between unmasked atoms of a molecule (get_fully_connected_edge_index, gcpnet.py:1062-1065)
-            m = 0;
-            for (int i = 0; i < nn[b]; ++i) m += node_mask[noff[b] + i] ? 1 : 0;
-            if (m == 0) return fail(h, "gcdm_plan_batch_masked: every molecule needs >= 1 unmasked atom (the reference's centroid is 0 / 0 otherwise)");
-            masked |= m != nn[b];
-        }
-        E += m * m;
-        max_n = std::max(max_n, (int)nn[b]);
-    }
-    if (!masked) node_mask = nullptr;
-    if (E >= (int64_t)1 << 31) return fail(h, "gcdm_plan_batch: too many edges");
-    // k_sample / k_prep stage one molecule in LDS (max_n * (3 + F) floats, 64 KB without an opt-in attribute)
-    if (max_n > 4096 || (size_t)max_n * h->D * sizeof(float) > 65536) return fail(h, "gcdm_plan_batch: molecule too large (max_n * (3 + F) floats must fit 64 KB of LDS)");
-    free_plan(h);                 // only now: a request rejected by the ARGUMENT checks above leaves the previous plan in place; one that fails
-                                  // below (workspace over 4 GB, hipMalloc) leaves NO plan (callers must not assume the old one survives:
-                                  // GCPNetDynamics.plan forgets its plan key before the call)
-    const int N = noff[B];
-    std::vector<int> erow(E), ecol(E), ncnt(N), rowstart(N);
-    int64_t p = 0;
-    std::vector<int> tvalid;
-    if (K > 0) tvalid.assign((size_t)((E + 63) / 64), 64);
-    for (int b = 0; b < B; ++b) {
-        const int o = noff[b], n = nn[b];
-        if (sub_first[b] && (p & 63)) {
-            tvalid[(size_t)(p >> 6)] = (int)(p & 63);
-            for (; p & 63; ++p) { erow[p] = erow[p - 1]; ecol[p] = ecol[p - 1]; }
-        }
-        int m = n;
-        if (node_mask) { m = 0; for (int i = 0; i < n; ++i) m += node_mask[o + i] ? 1 : 0; }
-        for (int i = 0; i < n; ++i) {
-            const bool on = !node_mask || node_mask[o + i];
-            ncnt[o + i] = on ? m : 0;           // a masked node has no edges: its aggregated row is zero (AggRow)
-            rowstart[o + i] = (int)p;
-            if (!on) continue;
-            for (int j = 0; j < n; ++j)
-                if (!node_mask || node_mask[o + j]) { erow[p] = o + i; ecol[p] = o + j; ++p; }
-        }
-    }
-    if (K > 0 && (p & 63)) tvalid[(size_t)(p >> 6)] = (int)(p & 63);
-    if (node_mask) {
-        std::vector<float> mf(N);
-        for (int i = 0; i < N; ++i) mf[i] = node_mask[i] ? 1.f : 0.f;
-        HIP_OK(h, hipMalloc(&h->d_mask, N * sizeof(float)));
-        HIP_OK(h, hipMemcpy(h->d_mask, mf.data(), N * sizeof(float), hipMemcpyHostToDevice));
-    }
-    HIP_OK(h, hipMalloc(&h->d_noff, (B + 1) * sizeof(int)));
-    HIP_OK(h, hipMalloc(&h->d_erow, E * sizeof(int)));
-    HIP_OK(h, hipMalloc(&h->d_ecol, E * sizeof(int)));
-    HIP_OK(h, hipMalloc(&h->d_ncnt, N * sizeof(int)));
-    HIP_OK(h, hipMalloc(&h->d_rowstart, N * sizeof(int)));
-    HIP_OK(h, hipMemcpy(h->d_rowstart, rowstart.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    HIP_OK(h, hipMemcpy(h->d_noff, noff.data(), (B + 1) * sizeof(int), hipMemcpyHostToDevice));
-    HIP_OK(h, hipMemcpy(h->d_erow, erow.data(), E * sizeof(int), hipMemcpyHostToDevice));
-    HIP_OK(h, hipMemcpy(h->d_ecol, ecol.data(), E * sizeof(int), hipMemcpyHostToDevice));
-    HIP_OK(h, hipMemcpy(h->d_ncnt, ncnt.data(), N * sizeof(int), hipMemcpyHostToDevice));
-    // workspace (all sub-buffers 16-byte aligned)
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n + 3) & ~size_t(3); return o; };
-    const size_t n = (size_t)N, e = (size_t)E;
-    const size_t oX0 = take(3 * n), oXC = take(3 * n), oFB = take(9 * n), oC0 = take(12 * n), oHIN = take(4 * h->FinG * n), oH4 = take(GCDM_S * n),
-                 oCHI = take(96 * n), oPQ = take(512 * n), oVDI = take((size_t)(h->H0 + 3) * 3 * n), oVDJ = take((size_t)(h->H0 + 3) * 3 * n),
-                 oAGG = take(GCDM_AGGW * n), oPART = take(((e + 31) / 32) * 2 * GCDM_AGGW), oVEL = take(3 * n), oEPS = take((size_t)h->D * n), oEP = take((size_t)h->Se * e),
-                 oAL = take((size_t)h->Ve * e), oU = take(3 * e), oFR = take(9 * e), oPROF = take(((e + 31) / 32) * 192),
-                 oX0SC = take(h->sc ? 3 * n : 0), oBL = take(h->sc ? (size_t)h->Ve * e : 0), oUSC = take(h->sc ? 3 * e : 0),
-                 oZK = take((size_t)h->D * n), oZU = take((size_t)h->D * n), oZROW = take(GCDM_AGGW),
-                 oPQb = take(512 * n), oVDIb = take((size_t)(h->H0 + 3) * 3 * n), oVDJb = take((size_t)(h->H0 + 3) * 3 * n);
-    h->ws_floats = off;
-    if (off * sizeof(float) >= ((size_t)1 << 32)) return fail(h, "gcdm_plan_batch: workspace exceeds 4 GB (buffer-addressed); split the batch");
-    HIP_OK(h, hipMalloc(&h->ws, off * sizeof(float)));
-    HIP_OK(h, hipMemset(h->ws, 0, off * sizeof(float)));
-    float* w = h->ws;
-    h->X0 = w + oX0; h->XC = w + oXC; h->FBAR = w + oFB; h->CHI0 = w + oC0; h->HIN4 = w + oHIN; h->H4 = w + oH4; h->CHI = w + oCHI;
-    h->PQ4 = w + oPQ; h->VDI = w + oVDI; h->VDJ = w + oVDJ; h->AGG = w + oAGG; h->PART = w + oPART; h->VEL = w + oVEL; h->EPS = w + oEPS; h->EP4 = w + oEP;
-    h->AL = w + oAL; h->U = w + oU; h->FR = w + oFR; h->PROF = w + oPROF;
-    h->ZK = w + oZK; h->ZU = w + oZU; h->ZROW = w + oZROW;     // ZROW is never written: the workspace starts zeroed
-    h->PQ4b = w + oPQb; h->VDIb = w + oVDIb; h->VDJb = w + oVDJb;
-    h->X0SC = h->sc ? w + oX0SC : nullptr; h->BL = h->sc ? w + oBL : nullptr; h->USC = h->sc ? w + oUSC : nullptr;
-    h->B = B; h->N = N; h->E = E; h->max_n = max_n;
-    h->E_real = 0;
-    for (int i = 0; i < N; ++i) h->E_real += ncnt[i];
-    if (K > 0) {            // packed plan: the same topology, plus the sub-batch of each molecule, the first node of each sub-batch, the seeds and the flag words
-      auto tables = [&]() -> int {
-        std::vector<int> mol_sub(B), sub_noff(K + 1, 0);
-        for (int k = 0, b = 0; k < K; ++k) {
-            for (int j = 0; j < mols_per_batch[k]; ++j, ++b) mol_sub[b] = k;
-            sub_noff[k + 1] = noff[b];
-        }
-        h->K = K;           // (from here on free_plan releases the tables)
-        HIP_OK(h, hipMalloc(&h->d_mol_sub, (size_t)B * sizeof(int)));
-        HIP_OK(h, hipMalloc(&h->d_sub_noff, (size_t)(K + 1) * sizeof(int)));
-        HIP_OK(h, hipMalloc(&h->d_seeds, (size_t)K * sizeof(uint64_t)));
-        HIP_OK(h, hipMalloc(&h->d_sub_flags, (size_t)K * sizeof(uint32_t)));
-        HIP_OK(h, hipMalloc(&h->d_tvalid, tvalid.size() * sizeof(int)));
-        HIP_OK(h, hipMemcpy(h->d_tvalid, tvalid.data(), tvalid.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIP_OK(h, hipMemcpy(h->d_mol_sub, mol_sub.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-        HIP_OK(h, hipMemcpy(h->d_sub_noff, sub_noff.data(), (size_t)(K + 1) * sizeof(int), hipMemcpyHostToDevice));
-        HIP_OK(h, hipMemset(h->d_seeds, 0, (size_t)K * sizeof(uint64_t)));
-        HIP_OK(h, hipMemset(h->d_sub_flags, 0, (size_t)K * sizeof(uint32_t)));
-        FlagBlock fb{};
-        fb.num_sub = (uint32_t)K; fb.sub_noff = h->d_sub_noff; fb.sub_flags = h->d_sub_flags;
-        HIP_OK(h, hipMemcpy(reinterpret_cast<char*>(h->d_flags) + offsetof(FlagBlock, num_sub), reinterpret_cast<const char*>(&fb) + offsetof(FlagBlock, num_sub),
-                            sizeof(FlagBlock) - offsetof(FlagBlock, num_sub), hipMemcpyHostToDevice));
-        return 0;
-      };
-      if (tables()) { free_plan(h); return -1; }          // (no plan rather than one with half its tables)
-    }
-    // ---- node-tile queues of the fused layer launch (gcdm_layer_x3.hip.h): 64-edge tiles, XCD x owns the x-th contiguous eighth of the tile list (the partition of
-    // k_edge_msg_x3's persistent loop); node tile t (T nodes) waits for the edge tiles first_tile(t) .. last_tile(t) of its rows and is owned by the XCD whose range
-    // contains first_tile(t).  A plan qualifies when nothing is masked, the launch is persistent and no node tile spans three XCDs.
-    h->tail_tiles32 = 0;
-    const int wgs_ = h->cus / 8 * 8;
-    if (!node_mask && K == 0 && E > (int64_t)64 * wgs_ && wgs_ >= 8) {          // (a packed plan runs two launches per layer: its padded edge list is not what the queues below describe)
-        const int G = (int)((E + 63) / 64), base = G >> 3, rem = G & 7;
-        int xs[9];
-        for (int x = 0; x <= 8; ++x) xs[x] = x * base + std::min(x, rem);
-        auto xcd_of_tile = [&](int g) { int x = 0; while (x < 7 && g >= xs[x + 1]) ++x; return x; };
-        constexpr int T = 32;                              // nodes per node tile of the tail role (NodeTailRole<32>)
-        const int NTt = (N + T - 1) / T;
-        std::vector<int> tab(64 + (size_t)NTt, 0);
-        std::vector<std::vector<std::pair<int, int>>> owned(8);          // per XCD: (edge tile the node item stands behind, node tile)
-        bool ok = true;
-        for (int t = 0; t < NTt && ok; ++t) {
-            const int nf = t * T, nl = std::min(nf + T, N) - 1;
-            const int ft = rowstart[nf] >> 6, lt = (rowstart[nl] + ncnt[nl] - 1) >> 6;
-            const int owner = xcd_of_tile(ft), xl = xcd_of_tile(lt);
-            if (xl > owner + 1 || lt - ft + 1 > 0xffff) ok = false;
-            tab[64 + t] = (lt - ft + 1) | ((xl != owner ? 1 : 0) << 16);
-            owned[owner].push_back({lt, t});
-        }
-        for (int x = 0; x < 8 && ok; ++x) {
-            tab[8 * x] = owned[x].empty() ? 0 : owned[x][0].second;
-            tab[8 * x + 1] = (int)owned[x].size();
-            tab[8 * x + 2] = xs[x + 1] - xs[x] + (int)owned[x].size();
-            if (x >= 1) {                                                // rows of XCD x's first tiles that belong to the boundary node tile owned by XCD x - 1
-                const int tb = erow[(size_t)xs[x] * 64] / T;
-                if ((rowstart[tb * T] >> 6) < xs[x]) tab[8 * x + 3] = std::min((tb + 1) * T, N);
-            }
-        }
-        if (ok) {
-            HIP_OK(h, hipMalloc(&h->d_tail_tab, tab.size() * sizeof(int)));
-            HIP_OK(h, hipMemcpy(h->d_tail_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
-        h->tail_tiles32 = (N + 31) / 32;
-        HIP_OK(h, hipMalloc(&h->d_tail_ctr, ((size_t)h->tail_tiles32 + TAIL_CTR_WORDS) * sizeof(int)));
-        HIP_OK(h, hipMemset(h->d_tail_ctr, 0, ((size_t)h->tail_tiles32 + TAIL_CTR_WORDS) * sizeof(int)));
-    }
+    PlanHost ph;
+    if (build_plan_host(h->dims(), B, nn, node_mask, K, mols_per_batch, ph, h->err)) return -1;      // refused by the ARGUMENT checks: the previous plan stays in place
+    const WsLayout wl = ws_layout(h->dims(), ph.N, ph.E);
+    // A request that fails below (workspace over 4 GB, an allocation, a copy) leaves NO plan (callers must not assume the old one survives: GCPNetDynamics.plan
+    // forgets its plan key before the call).  The old plan goes before the new one is allocated: the two are never resident together.
+    if (h->plan.K) (void)write_flag_block_pack(h, FlagBlock{});
+    h->plan = Plan{};
+    if (!wl.err.empty()) return fail(h, wl.err);
+    Plan p;
+    if (upload_plan(h, ph, wl, p)) return -1;
+    h->plan = std::move(p);
     return 0;
 }
 
@@ -1319,8 +1196,8 @@ int gcdm_bond_orders(const GcdmBondTables* tables, const float* x, int64_t x_row
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int64_t gcdm_num_nodes(const gcdm_handle* h) { return h ? h->N : -1; }
-int64_t gcdm_num_edges(const gcdm_handle* h) { return h ? h->E_real : -1; }
+int64_t gcdm_num_nodes(const gcdm_handle* h) { return h ? h->plan.N : -1; }
+int64_t gcdm_num_edges(const gcdm_handle* h) { return h ? h->plan.E_real : -1; }
 
 int gcdm_debug_set_layer_limit(gcdm_handle* h, int32_t n) {
     if (!h) return -1;
@@ -1338,7 +1215,7 @@ int gcdm_forward(gcdm_handle* h, const float* xh, const float* t, const float* c
 int gcdm_forward_sc(gcdm_handle* h, const float* xh, const float* xh_sc, const float* t, const float* context, float* out, uint32_t* flags,
                     void* stream_) {
     if (!h) return -1;
-    if (h->K) return refuse_packed(h, "gcdm_forward_sc");
+    if (h->plan.K) return refuse_packed(h, "gcdm_forward_sc");
     if (!t) return fail(h, "gcdm_forward: null tensor");
     return forward_impl(h, xh, xh_sc, t, nullptr, context, out, flags, stream_);
 }
@@ -1360,39 +1237,39 @@ int32_t gcdm_timestep_index(float t, int32_t num_timesteps) {
 static float gamma_lookup(const gcdm_handle* h, float t) { return h->gamma[gcdm_timestep_index(t, h->cfg.num_timesteps)]; }
 
 static int launch_sample(gcdm_handle* h, StepArgs& sa, hipStream_t st) {
-    if (h->d_mask) return fail(h, "the sampler entry points need an all-True node mask (plan with gcdm_plan_batch); masked plans serve gcdm_forward only");
+    if (need_unmasked(h)) return -1;
     DeviceGuard guard(h->cfg.device);
-    sa.noff = h->d_noff; sa.N = h->N; sa.D = h->D; sa.node_base = h->node_base;
-    sa.pack = h->pack();
+    sa.noff = h->plan.d_noff; sa.N = h->plan.N; sa.D = h->D; sa.node_base = h->node_base;
+    sa.pack = h->plan.pack();
     if (h->fix_noise) {                 // pre-pass: mean of this draw over all nodes (deterministic order)
-        if (!h->d_gmean) HIP_OK(h, hipMalloc(&h->d_gmean, 4 * sizeof(float)));
-        hipLaunchKernelGGL(k_noise_mean, dim3(1), dim3(1024), 0, st, sa.noise, sa.seed, sa.draw, h->node_base, h->N, h->D, h->d_gmean);
+        if (!h->d_gmean) HIP_OK(h, h->d_gmean.alloc(4));
+        hipLaunchKernelGGL(k_noise_mean, dim3(1), dim3(1024), 0, st, sa.noise, sa.seed, sa.draw, h->node_base, h->plan.N, h->D, h->d_gmean);
         sa.gmean = h->d_gmean;
     }
-    hipLaunchKernelGGL(k_sample, dim3(h->B), dim3(64), (size_t)h->max_n * h->D * sizeof(float), st, sa);
+    hipLaunchKernelGGL(k_sample, dim3(h->plan.B), dim3(64), (size_t)h->plan.max_n * h->D * sizeof(float), st, sa);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
 
 int gcdm_sample_init(gcdm_handle* h, float* z, const float* noise, uint64_t seed, void* stream_) {
-    if (!h || !z || !h->N) return fail(h, "gcdm_sample_init: bad argument / no plan");
+    if (!h || !z || !h->planned()) return fail(h, "gcdm_sample_init: bad argument / no plan");
     StepArgs sa{};
     sa.z = z; sa.noise = noise; sa.seed = seed; sa.draw = 0x7fffffffu; sa.mode = 1; sa.flags_dev = h->d_flags;
     return launch_sample(h, sa, (hipStream_t)stream_);
 }
 
 int gcdm_encode_samples(gcdm_handle* h, const float* xh, float* z, uint32_t* flags, void* stream_) {
-    if (!h || !xh || !z || !h->N) return fail(h, "gcdm_encode_samples: bad argument / no plan");
-    if (h->K) return refuse_packed(h, "gcdm_encode_samples");
+    if (!h || !xh || !z || !h->planned()) return fail(h, "gcdm_encode_samples: bad argument / no plan");
+    if (h->plan.K) return refuse_packed(h, "gcdm_encode_samples");
     DeviceGuard guard(h->cfg.device);
     hipStream_t st = (hipStream_t)stream_;
     HIP_OK(h, hipMemsetAsync(h->d_flags + 1, 0, 2 * sizeof(uint32_t), st));
     EncodeArgs ea{};
-    ea.xh = xh; ea.z = z; ea.noff = h->d_noff; ea.D = h->D; ea.num_atom_types = h->cfg.num_atom_types; ea.include_charges = h->cfg.include_charges;
+    ea.xh = xh; ea.z = z; ea.noff = h->plan.d_noff; ea.D = h->D; ea.num_atom_types = h->cfg.num_atom_types; ea.include_charges = h->cfg.include_charges;
     ea.nv0 = h->cfg.norm_values[0]; ea.nv1 = h->cfg.norm_values[1]; ea.nv2 = h->cfg.norm_values[2];
     ea.nb1 = h->cfg.norm_biases[1]; ea.nb2 = h->cfg.norm_biases[2];
     ea.stat = h->d_flags + 1;
-    hipLaunchKernelGGL(k_encode, dim3(h->B), dim3(64), 0, st, ea);
+    hipLaunchKernelGGL(k_encode, dim3(h->plan.B), dim3(64), 0, st, ea);
     if (flags) hipLaunchKernelGGL(k_mean_flag, dim3(1), dim3(1), 0, st, h->d_flags + 1, flags);
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -1423,15 +1300,15 @@ static StepRow step_row(const gcdm_handle* h, float s, float t, uint32_t draw) {
 static int transition(gcdm_handle* h, const float* z_in, float* z_out, const float* sc, const float* context, float s, float t,
                       const float* noise, uint64_t seed, uint32_t draw, uint32_t* flags, void* stream_) {
     hipStream_t st = (hipStream_t)stream_;
-    if (h->d_mask) return fail(h, "the sampler entry points need an all-True node mask (plan with gcdm_plan_batch); masked plans serve gcdm_forward only");
+    if (need_unmasked(h)) return -1;
     // the step being captured into a graph: t and the coefficients come from the device table at run time
-    const StepFeed feed{h->capturing ? h->d_rows : nullptr, h->capturing ? h->d_cursor : nullptr, t};
-    if (forward_impl(h, z_in, sc, nullptr, &feed, context, h->EPS, flags, stream_)) return -1;
+    const StepFeed feed{h->capturing ? h->d_rows.p : nullptr, h->capturing ? h->d_cursor.p : nullptr, t};
+    if (forward_impl(h, z_in, sc, nullptr, &feed, context, h->plan.EPS, flags, stream_)) return -1;
     const StepRow r = step_row(h, s, t, draw);
     StepArgs sa{};
     if (h->capturing) { sa.rows = h->d_rows; sa.cursor = h->d_cursor + 1; sa.cursor_rw = h->d_cursor; }
-    sa.VEL = h->VEL;
-    sa.z = const_cast<float*>(z_in); sa.z_out = z_out; sa.eps = h->EPS; sa.noise = noise; sa.seed = seed; sa.draw = draw; sa.mode = 0;
+    sa.VEL = h->plan.VEL;
+    sa.z = const_cast<float*>(z_in); sa.z_out = z_out; sa.eps = h->plan.EPS; sa.noise = noise; sa.seed = seed; sa.draw = draw; sa.mode = 0;
     sa.alpha_coef = r.alpha_coef;
     sa.c_eps = r.c_eps;
     sa.sigma = r.sigma;
@@ -1444,7 +1321,7 @@ static int transition(gcdm_handle* h, const float* z_in, float* z_out, const flo
 static int step_via_graph(gcdm_handle* h, float* z, const float* context, int32_t s_index, int32_t num_steps, uint64_t seed, uint32_t* flags,
                           hipStream_t st) {
     if (!h->step_graph || h->step_graph_failed || h->fix_noise || h->profile || h->profile_phases || h->profile_node || h->layer_limit >= 0 || h->sc ||
-        h->d_mask || !h->N)
+        h->plan.d_mask || !h->planned())
         return 0;
     DeviceGuard guard(h->cfg.device);
     auto give_up = [&](const char* what, hipError_t e) {
@@ -1457,13 +1334,12 @@ static int step_via_graph(gcdm_handle* h, float* z, const float* context, int32_
     };
     hipError_t e;
     if (!h->cap_stream && (e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking)) != hipSuccess) return give_up("hipStreamCreate", e);
-    if (!h->d_cursor && (e = hipMalloc(&h->d_cursor, 2 * sizeof(int))) != hipSuccess) return give_up("hipMalloc", e);      // two slots (k_cursor_set)
+    if (!h->d_cursor && (e = h->d_cursor.alloc(2)) != hipSuccess) return give_up("hipMalloc", e);      // two slots (k_cursor_set)
     if (h->rows_steps != num_steps) {              // the table of this step count (s = i / num_steps, t = (i + 1) / num_steps, as gcdm_sample_step_to)
         std::vector<StepRow> rows((size_t)num_steps);
         for (int i = 0; i < num_steps; ++i) rows[i] = step_row(h, (float)i / (float)num_steps, (float)(i + 1) / (float)num_steps, (uint32_t)i);
-        if (h->d_rows) { wait_step_graph_idle(h); (void)hipFree(h->d_rows); h->d_rows = nullptr; }     // (a graph still reading the old table: whatever stream it was launched on)
-        if ((e = hipMalloc(&h->d_rows, rows.size() * sizeof(StepRow))) != hipSuccess) return give_up("hipMalloc", e);
-        if ((e = hipMemcpy(h->d_rows, rows.data(), rows.size() * sizeof(StepRow), hipMemcpyHostToDevice)) != hipSuccess) return give_up("hipMemcpy", e);
+        if (h->d_rows) wait_step_graph_idle(h);     // a graph still reading the old table (whatever stream it was launched on) comes first; upload() then frees it
+        if ((e = h->d_rows.upload(rows)) != hipSuccess) return give_up(h->d_rows ? "hipMemcpy" : "hipMalloc", e);
         if (h->sg.exec) { wait_step_graph_idle(h); (void)hipGraphExecDestroy(h->sg.exec); (void)hipGraphDestroy(h->sg.graph); h->sg = gcdm_handle::StepGraph{}; }
         h->rows_steps = num_steps;
     }
@@ -1508,9 +1384,9 @@ static int step_via_graph(gcdm_handle* h, float* z, const float* context, int32_
 int gcdm_sample_step_to(gcdm_handle* h, const float* z_in, float* z_out, const float* context, int32_t s_index, int32_t num_steps,
                         const float* noise, uint64_t seed, uint32_t* flags, void* stream_) {
     if (!h || !z_in || !z_out || num_steps <= 0 || s_index < 0 || s_index >= num_steps) return fail(h, "gcdm_sample_step: bad argument");
-    if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_sample_step: gamma table not set");
+    if (need_gamma(h, "gcdm_sample_step")) return -1;
     // s = s_index / num_steps, t = (s_index + 1) / num_steps (variational_diffusion.py:1335-1341); t [N] = t[batch_index] (:1239)
-    if (h->K) seed = 0;                // packed plan: the seeds are the table's (gcdm_set_batch_seeds); one value here, so that the captured step is not re-captured per caller seed
+    if (h->plan.K) seed = 0;                // packed plan: the seeds are the table's (gcdm_set_batch_seeds); one value here, so that the captured step is not re-captured per caller seed
     if (z_in == z_out && !noise) {
         const int g = step_via_graph(h, z_out, context, s_index, num_steps, seed, flags, (hipStream_t)stream_);
         if (g != 0) return g < 0 ? -1 : 0;
@@ -1522,9 +1398,9 @@ int gcdm_sample_step_to(gcdm_handle* h, const float* z_in, float* z_out, const f
 int gcdm_sample_step_sc(gcdm_handle* h, float* z, float* self_cond, int32_t have_self_cond, const float* context, int32_t s_index,
                         int32_t num_steps, const float* noise, const float* noise_self_cond, uint64_t seed, uint32_t* flags, void* stream_) {
     if (!h || !z || !self_cond || num_steps <= 0 || s_index < 0 || s_index >= num_steps) return fail(h, "gcdm_sample_step_sc: bad argument");
-    if (h->K) return refuse_packed(h, "gcdm_sample_step_sc");
+    if (h->plan.K) return refuse_packed(h, "gcdm_sample_step_sc");
     if (!h->sc) return fail(h, "gcdm_sample_step_sc: the handle was created without self_condition");
-    if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_sample_step_sc: gamma table not set");
+    if (need_gamma(h, "gcdm_sample_step_sc")) return -1;
     const float s = (float)s_index / (float)num_steps, t = (float)(s_index + 1) / (float)num_steps;
     // z_s ~ p(z_s | z_t, previous estimate) (:1343-1352)
     if (transition(h, z, z, have_self_cond ? self_cond : nullptr, context, s, t, noise, seed, (uint32_t)s_index, flags, stream_)) return -1;
@@ -1542,24 +1418,24 @@ int gcdm_sample_final(gcdm_handle* h, const float* z0, const float* context, con
 
 int gcdm_sample_final_sc(gcdm_handle* h, const float* z0, const float* self_cond, const float* context, const float* noise, uint64_t seed,
                          float* out, uint32_t* flags, void* stream_) {
-    if (h && h->K) return refuse_packed(h, "gcdm_sample_final_sc");
+    if (h && h->plan.K) return refuse_packed(h, "gcdm_sample_final_sc");
     return sample_final_impl(h, z0, self_cond, context, noise, seed, out, flags, stream_);
 }
 
 static int sample_final_impl(gcdm_handle* h, const float* z0, const float* self_cond, const float* context, const float* noise, uint64_t seed,
                              float* out, uint32_t* flags, void* stream_) {
     if (!h || !z0 || !out) return fail(h, "gcdm_sample_final: bad argument");
-    if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_sample_final: gamma table not set");
+    if (need_gamma(h, "gcdm_sample_final")) return -1;
     DeviceGuard guard(h->cfg.device);
     hipStream_t st = (hipStream_t)stream_;
-    if (h->d_mask) return fail(h, "the sampler entry points need an all-True node mask (plan with gcdm_plan_batch); masked plans serve gcdm_forward only");
+    if (need_unmasked(h)) return -1;
     const StepFeed feed{nullptr, nullptr, 0.0f};
-    if (forward_impl(h, z0, self_cond, nullptr, &feed, context, h->EPS, flags, stream_)) return -1;
+    if (forward_impl(h, z0, self_cond, nullptr, &feed, context, h->plan.EPS, flags, stream_)) return -1;
     const float g0 = gamma_lookup(h, 0.0f);
     const float sigma_x = expf(0.5f * g0);                       // SNR(-0.5 * gamma_0)   (:855-859)
     const float sig0 = sqrtf(sigmoidf_(g0)), alp0 = sqrtf(sigmoidf_(-g0));
     StepArgs sa{};
-    sa.z = const_cast<float*>(z0); sa.eps = h->EPS; sa.VEL = h->VEL; sa.noise = noise; sa.seed = seed; sa.draw = 0x7ffffffeu; sa.mode = 2;
+    sa.z = const_cast<float*>(z0); sa.eps = h->plan.EPS; sa.VEL = h->plan.VEL; sa.noise = noise; sa.seed = seed; sa.draw = 0x7ffffffeu; sa.mode = 2;
     sa.alpha_coef = 1.0f / alp0; sa.c_eps = sig0; sa.sigma = sigma_x;
     sa.out = out; sa.num_atom_types = h->cfg.num_atom_types; sa.include_charges = h->cfg.include_charges;
     sa.nv0 = h->cfg.norm_values[0]; sa.nv1 = h->cfg.norm_values[1]; sa.nv2 = h->cfg.norm_values[2];
@@ -1567,17 +1443,17 @@ static int sample_final_impl(gcdm_handle* h, const float* z0, const float* self_
     sa.user_flags = flags; sa.flags_dev = h->d_flags;
     if (launch_sample(h, sa, st)) return -1;
     // CoG drift re-projection is a whole-batch decision in the reference (:1389-1402); only "for examples without intermediate states"
-    if (h->cog_fix) hipLaunchKernelGGL(k_cog_fix, dim3(h->B), dim3(64), 0, st, out, h->d_noff, h->D, h->d_flags, flags, h->pack());
+    if (h->cog_fix) hipLaunchKernelGGL(k_cog_fix, dim3(h->plan.B), dim3(64), 0, st, out, h->plan.d_noff, h->D, h->d_flags, flags, h->plan.pack());
     HIP_OK(h, hipGetLastError());
     return 0;
 }
 
 // ---- RePaint inpainting (variational_diffusion.py:1582-1789) ----
 int gcdm_inpaint_center(gcdm_handle* h, const float* xh, const uint8_t* fixed, float* xh0, void* stream_) {
-    if (!h || !xh || !fixed || !xh0 || !h->N) return fail(h, "gcdm_inpaint_center: bad argument / no plan");
-    if (h->K) return refuse_packed(h, "gcdm_inpaint_center");
+    if (!h || !xh || !fixed || !xh0 || !h->planned()) return fail(h, "gcdm_inpaint_center: bad argument / no plan");
+    if (h->plan.K) return refuse_packed(h, "gcdm_inpaint_center");
     DeviceGuard guard(h->cfg.device);
-    hipLaunchKernelGGL(k_inpaint_center, dim3(h->B), dim3(64), 0, (hipStream_t)stream_, xh, fixed, h->d_noff, h->D, xh0);
+    hipLaunchKernelGGL(k_inpaint_center, dim3(h->plan.B), dim3(64), 0, (hipStream_t)stream_, xh, fixed, h->plan.d_noff, h->D, xh0);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
@@ -1585,33 +1461,33 @@ int gcdm_inpaint_center(gcdm_handle* h, const float* xh, const uint8_t* fixed, f
 int gcdm_inpaint_step(gcdm_handle* h, float* z, const float* xh0, const uint8_t* fixed, float* self_cond, int32_t have_self_cond,
                       const float* context, int32_t s_index, int32_t num_steps, const float* noise_known, const float* noise_unknown,
                       const float* noise_self_cond, uint64_t seed, uint32_t draw_base, uint32_t* flags, void* stream_) {
-    if (!h || !z || !xh0 || !fixed || num_steps <= 0 || s_index < 0 || s_index >= num_steps || !h->N) return fail(h, "gcdm_inpaint_step: bad argument / no plan");
-    if (h->K) return refuse_packed(h, "gcdm_inpaint_step");
+    if (!h || !z || !xh0 || !fixed || num_steps <= 0 || s_index < 0 || s_index >= num_steps || !h->planned()) return fail(h, "gcdm_inpaint_step: bad argument / no plan");
+    if (h->plan.K) return refuse_packed(h, "gcdm_inpaint_step");
     if ((h->sc != 0) != (self_cond != nullptr)) return fail(h, "gcdm_inpaint_step: self_cond must be given exactly when the handle has self_condition");
-    if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_inpaint_step: gamma table not set");
+    if (need_gamma(h, "gcdm_inpaint_step")) return -1;
     DeviceGuard guard(h->cfg.device);
     hipStream_t st = (hipStream_t)stream_;
     const float s = (float)s_index / (float)num_steps, t = (float)(s_index + 1) / (float)num_steps;
     // known nodes: q(z_s | x, h) of the given molecule (compute_noised_representation, :910-931)
     const float gs = gamma_lookup(h, s);
     StepArgs sa{};
-    sa.z = const_cast<float*>(xh0); sa.z_out = h->ZK; sa.noise = noise_known; sa.seed = seed; sa.draw = draw_base; sa.mode = 3;
+    sa.z = const_cast<float*>(xh0); sa.z_out = h->plan.ZK; sa.noise = noise_known; sa.seed = seed; sa.draw = draw_base; sa.mode = 3;
     sa.alpha_coef = sqrtf(sigmoidf_(-gs)); sa.sigma = sqrtf(sigmoidf_(gs));
     sa.user_flags = flags; sa.flags_dev = h->d_flags;
     if (launch_sample(h, sa, st)) return -1;
     // everything: one ancestral step of the model (:1652-1662), then the next self-conditioning estimate from it (:1664-1676)
-    if (transition(h, z, h->ZU, (self_cond && have_self_cond) ? self_cond : nullptr, context, s, t, noise_unknown, seed, draw_base + 1, flags, stream_)) return -1;
-    if (self_cond && transition(h, h->ZU, self_cond, nullptr, context, 0.0f, s, noise_self_cond, seed, draw_base + 2, flags, stream_)) return -1;
-    hipLaunchKernelGGL(k_inpaint_combine, dim3(h->B), dim3(64), 0, st, h->ZK, h->ZU, fixed, h->d_noff, h->D, z);
+    if (transition(h, z, h->plan.ZU, (self_cond && have_self_cond) ? self_cond : nullptr, context, s, t, noise_unknown, seed, draw_base + 1, flags, stream_)) return -1;
+    if (self_cond && transition(h, h->plan.ZU, self_cond, nullptr, context, 0.0f, s, noise_self_cond, seed, draw_base + 2, flags, stream_)) return -1;
+    hipLaunchKernelGGL(k_inpaint_combine, dim3(h->plan.B), dim3(64), 0, st, h->plan.ZK, h->plan.ZU, fixed, h->plan.d_noff, h->D, z);
     HIP_OK(h, hipGetLastError());
     return 0;
 }
 
 int gcdm_inpaint_jump(gcdm_handle* h, float* z, int32_t s_index, int32_t t_index, int32_t num_steps, const float* noise, uint64_t seed,
                       uint32_t draw, void* stream_) {
-    if (!h || !z || num_steps <= 0 || s_index < 0 || t_index <= s_index || t_index > num_steps || !h->N) return fail(h, "gcdm_inpaint_jump: bad argument / no plan");
-    if (h->K) return refuse_packed(h, "gcdm_inpaint_jump");
-    if ((int64_t)h->gamma.size() != (int64_t)h->cfg.num_timesteps + 1) return fail(h, "gcdm_inpaint_jump: gamma table not set");
+    if (!h || !z || num_steps <= 0 || s_index < 0 || t_index <= s_index || t_index > num_steps || !h->planned()) return fail(h, "gcdm_inpaint_jump: bad argument / no plan");
+    if (h->plan.K) return refuse_packed(h, "gcdm_inpaint_jump");
+    if (need_gamma(h, "gcdm_inpaint_jump")) return -1;
     // q(z_t | z_s) (sample_p_zt_given_zs, :1163-1201; sigma_and_alpha_t_given_s :342-367)
     const float gs = gamma_lookup(h, (float)s_index / (float)num_steps), gt = gamma_lookup(h, (float)t_index / (float)num_steps);
     StepArgs sa{};
@@ -1623,10 +1499,10 @@ int gcdm_inpaint_jump(gcdm_handle* h, float* z, int32_t s_index, int32_t t_index
 }
 
 int gcdm_unnormalize_z(gcdm_handle* h, const float* z, float* out, void* stream_) {
-    if (!h || !z || !out || !h->N) return fail(h, "gcdm_unnormalize_z: bad argument / no plan");
+    if (!h || !z || !out || !h->planned()) return fail(h, "gcdm_unnormalize_z: bad argument / no plan");
     DeviceGuard guard(h->cfg.device);
-    const int total = h->N * h->D;
-    hipLaunchKernelGGL(k_unnormalize, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream_, z, out, h->N, h->D, h->cfg.num_atom_types,
+    const int total = h->plan.N * h->D;
+    hipLaunchKernelGGL(k_unnormalize, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream_, z, out, h->plan.N, h->D, h->cfg.num_atom_types,
                        h->cfg.norm_values[0], h->cfg.norm_values[1], h->cfg.norm_values[2], h->cfg.norm_biases[1], h->cfg.norm_biases[2]);
     HIP_OK(h, hipGetLastError());
     return 0;
@@ -1641,7 +1517,7 @@ int gcdm_set_option(gcdm_handle* h, const char* name, int32_t value) {
     if (k == "cog_fix") { h->cog_fix = value ? 1 : 0; return 0; }
     // (the getters of the options below return the stored field itself -- edge_tile: the effective tile, which is what a captured step bakes in; an option whose
     //  getter normalises its value must be added to the always-drop list beside mfma_mode)
-    if (h->K && value != 0 && (k == "fix_noise" || k == "flat_prev" || k == "flat_next" || k == "node_base")) return refuse_packed(h, ("gcdm_set_option(" + k + ")").c_str());
+    if (h->plan.K && value != 0 && (k == "fix_noise" || k == "flat_prev" || k == "flat_next" || k == "node_base")) return refuse_packed(h, ("gcdm_set_option(" + k + ")").c_str());
     if (gcdm_get_option(h, name) != value || k == "mfma_mode" || k == "fuse_node") drop_step_graph(h);
     if (k == "mfma_mode") {                 // 0: fp32 MFMA, 1: split-precision f16 x3 (fp32-equivalent, 5.3x the matrix rate)
         if (value != 0 && value != 1) return fail(h, "gcdm_set_option(mfma_mode): 0 or 1");
@@ -1685,7 +1561,7 @@ int gcdm_get_option(const gcdm_handle* h, const char* name) {
     if (k == "node_tile") return h->node_tile;
     if (k == "step_graph") return (h->step_graph && !h->step_graph_failed) ? 1 : 0;
     if (k == "graph_launches") return (int)(h->graph_launches & 0x7fffffff);
-    if (k == "num_batches") return h->K;
+    if (k == "num_batches") return h->plan.K;
     return -1;
 }
 
@@ -1735,16 +1611,13 @@ int gcdm_profile_node_kernel_ms(gcdm_handle* h, double* total_ms, int32_t* launc
 }
 
 int64_t gcdm_debug_read(gcdm_handle* h, const char* name, float* host_out, int64_t capacity) {
-    if (!h || !name || !h->N) return fail(h, "gcdm_debug_read: bad argument / no plan");
-    const int64_t n = h->N, e = h->E;
+    if (!h || !name || !h->planned()) return fail(h, "gcdm_debug_read: bad argument / no plan");
+    const int64_t n = h->plan.N, e = h->plan.E;
     const std::string k(name);
     const float* p = nullptr;
     int64_t cnt = 0;
-    if (k == "h") { p = h->H4; cnt = GCDM_S * n; }
-    else if (k == "chi") { p = h->CHI; cnt = 96 * n; }
-    else if (k == "x") { p = h->XC; cnt = 3 * n; }
-    else if (k == "x0") { p = h->X0; cnt = 3 * n; }
-    else if (k == "agg") {              // assembled on the host: whole rows from AGG, cut rows = their partial sums in tile order (AggSrc)
+    const WsLayout wl = ws_layout(h->dims(), n, e);
+    if (k == "agg") {             // assembled on the host: whole rows from AGG, cut rows = their partial sums in tile order (AggSrc)
         cnt = GCDM_AGGW * n;
         if (!host_out) return cnt;
         if (capacity < cnt) return fail(h, "gcdm_debug_read: capacity too small");
@@ -1753,10 +1626,10 @@ int64_t gcdm_debug_read(gcdm_handle* h, const char* name, float* host_out, int64
         const int64_t tiles = (e + ET - 1) / ET;
         std::vector<float> part((size_t)tiles * 2 * GCDM_AGGW);
         std::vector<int> rs(n), nc(n);
-        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host_out, h->AGG, cnt * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(part.data(), h->PART, part.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(rs.data(), h->d_rowstart, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(nc.data(), h->d_ncnt, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host_out, h->plan.AGG, cnt * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(part.data(), h->plan.PART, part.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(rs.data(), h->plan.d_rowstart, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(nc.data(), h->plan.d_ncnt, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
             return fail(h, "gcdm_debug_read: copy failed");
         for (int64_t i = 0; i < n; ++i) {
             float* dst = host_out + i * GCDM_AGGW;
@@ -1773,21 +1646,12 @@ int64_t gcdm_debug_read(gcdm_handle* h, const char* name, float* host_out, int64
         }
         return cnt;
     }
-    else if (k == "ep") { p = h->EP4; cnt = (int64_t)h->Se * e; }
-    else if (k == "alpha") { p = h->AL; cnt = (int64_t)h->Ve * e; }
-    else if (k == "u") { p = h->U; cnt = 3 * e; }
-    else if (k == "frames") { p = h->FR; cnt = 9 * e; }
-    else if (k == "pq") { p = h->PQ4; cnt = 512 * n; }
-    else if (k == "vdi") { p = h->VDI; cnt = (int64_t)(h->H0 + 3) * 3 * n; }
-    else if (k == "vdj") { p = h->VDJ; cnt = (int64_t)(h->H0 + 3) * 3 * n; }
-    else if (k == "hin") { p = h->HIN4; cnt = 4 * (int64_t)h->FinG * n; }
-    else if (k == "fbar") { p = h->FBAR; cnt = 9 * n; }
-    else if (k == "chi0") { p = h->CHI0; cnt = (h->sc ? 12 : 6) * n; }
-    else if (k == "vel") { p = h->VEL; cnt = 3 * n; }
-    else if (k == "erow") { p = (const float*)h->d_erow; cnt = e; }        // int32 bit patterns (edge list of the plan: row / col node per flat edge)
-    else if (k == "ecol") { p = (const float*)h->d_ecol; cnt = e; }
-    else if (k == "phase") { p = h->PROF; cnt = ((e + h->tile() - 1) / h->tile()) * 192; }
-    else if (k == "phase_node") { p = h->PROF; cnt = ((n + NT_ - 1) / NT_) * 192; }
+    else if (const WsEntry* b = wl.find(k)) { p = h->plan.ws.p + b->off; cnt = (int64_t)b->floats; }      // a whole sub-buffer, under its name in the workspace table
+    else if (k == "chi0") { p = h->plan.CHI0; cnt = (h->sc ? 12 : 6) * n; }
+    else if (k == "erow") { p = (const float*)h->plan.d_erow.p; cnt = e; }        // int32 bit patterns (edge list of the plan: row / col node per flat edge)
+    else if (k == "ecol") { p = (const float*)h->plan.d_ecol.p; cnt = e; }
+    else if (k == "phase") { p = h->plan.PROF; cnt = ((e + h->tile() - 1) / h->tile()) * 192; }
+    else if (k == "phase_node") { p = h->plan.PROF; cnt = ((n + NT_ - 1) / NT_) * 192; }
     else return fail(h, "gcdm_debug_read: unknown buffer " + k);
     if (!host_out) return cnt;
     if (capacity < cnt) return fail(h, "gcdm_debug_read: capacity too small");
@@ -1799,9 +1663,9 @@ int64_t gcdm_debug_read(gcdm_handle* h, const char* name, float* host_out, int64
 }
 
 double gcdm_forward_flops_executed(const gcdm_handle* h) {
-    if (!h || !h->N) return 0.0;
+    if (!h || !h->planned()) return 0.0;
     // multiply-adds actually issued per forward (x2; a split-precision product block counts once, padded MFMA rows / columns count), see DESIGN.md section 4
-    const double N = h->N, E = (double)h->E, S = GCDM_S, V = GCDM_V, Se = h->Se, Ve = h->Ve, H0 = h->H0;
+    const double N = h->plan.N, E = (double)h->plan.E, S = GCDM_S, V = GCDM_V, Se = h->Se, Ve = h->Ve, H0 = h->H0;
     const double G0 = h->m.layers.empty() ? 0 : h->m.layers[0].edge.base.G0;
     const bool x3 = h->use_x3();
     // fp32 kernels: extended-K GEMM + gate + VALU vector products; split-precision kernels: 16-deep k-blocks, vector path on 16x16x32 MFMA tiles

@@ -324,7 +324,7 @@ class GCPNetDynamics(nn.Module):
             key = key + (mk.numpy().tobytes(),)
         if key == self._plan_key:
             return
-        self._plan_key = None          # a rejected request leaves NO plan behind (the library drops the old one first)
+        self._plan_key = None          # a request that fails past the library's argument checks leaves NO plan behind (the old one goes before the new one is allocated)
         if mk is None:
             st = self._lib.gcdm_plan_batch(self._handle, len(nn_), C.c_void_p(nn_.data_ptr()))
         else:

@@ -82,7 +82,10 @@ int gcdm_set_gamma(gcdm_handle* h, const float* host_gamma, int64_t numel);
 
 /* Batch topology: B molecules with num_nodes[b] atoms each, flat node order = molecule-major (the order
  * `num_nodes_to_batch_index` produces, components/__init__.py:314-321).  Builds CSR offsets / tile lists once;
- * topology is constant over the 1000 steps.  Replaces get_fully_connected_edge_index (gcpnet.py:1054-1066). */
+ * topology is constant over the 1000 steps.  Replaces get_fully_connected_edge_index (gcpnet.py:1054-1066).
+ * On failure (all three plan calls): a request refused by the argument checks (a molecule without atoms / without an unmasked atom, too many edges, a
+ * molecule too large) leaves the previous plan in place; one that fails later (workspace >= 4 GB, an allocation, a copy) leaves the handle with NO plan
+ * -- never with part of one: the old plan is released before the new one is allocated. */
 int gcdm_plan_batch(gcdm_handle* h, int32_t num_molecules, const int32_t* host_num_nodes);
 
 /* The same with masked nodes (`batch.mask` with False entries, gcpnet.py:1081-1099, 1062-1065): node_mask host uint8 [sum num_nodes], 0 = masked

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import plan_ref
 import synth
 from oracle import gcdm_oracle as O
 
@@ -972,6 +973,57 @@ def test_failed_finalize_leaves_the_handle_refusing_and_a_correct_one_restores_t
     assert lib.gcdm_get_option(h, b"mfma_mode") == mode
     st, again = forward()
     assert st == 0 and again == first
+
+
+def test_plan_requests_keep_replace_or_drop_the_plan_as_a_whole():
+    """The failure contract of the plan calls: a request refused by the argument checks leaves the previous plan in place, one refused later (a workspace
+    over 4 GB: no device allocation is tried, nothing is launched) leaves NO plan, the handle plans again afterwards, and an ordinary plan behind a packed
+    one finds nothing of it left.  Every forward on plan [4, 5] gives the same bytes."""
+    net, W, _ = _net("qm9", seed=3, scale=0.25)
+    dev = torch.device("cuda")
+    net._ensure_handle(dev); net.sync_weights()
+    lib, h = net._lib, net._handle
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda a: C.c_void_p(a.data_ptr())
+    xh, t, _, _, _ = synth.make_inputs([4, 5], synth.dims_feat(_dims("qm9")), seed=2)
+    xh, t = xh.to(dev).contiguous(), t.to(dev).reshape(-1).contiguous()
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)
+
+    def plan(nn):
+        nn = i32(nn)
+        return lib.gcdm_plan_batch(h, len(nn), ptr(nn))
+
+    def forward():                      # (the flag word: the net's own, which read_flags() reports)
+        out = torch.full_like(xh, float("nan"))
+        st = lib.gcdm_forward(h, ptr(xh), ptr(t), None, ptr(out), ptr(net._flags), stream)
+        torch.cuda.synchronize()
+        return st, out.cpu().numpy().tobytes()
+
+    assert plan([4, 5]) == 0, lib.gcdm_last_error(h)
+    st, first = forward()
+    assert st == 0 and np.isfinite(np.frombuffer(first, dtype=np.float32)).all()
+    # refused by an argument check: the plan stays
+    assert plan([4, 0, 5]) < 0 and b">= 1 atom" in lib.gcdm_last_error(h)
+    assert lib.gcdm_num_nodes(h) == 9
+    assert forward() == (0, first)
+    # refused behind them: no plan
+    b = plan_ref.first_count_over_4gb(plan_ref.DIMS["qm9"], 75)
+    assert plan_ref.ws_offsets(plan_ref.DIMS["qm9"], 75 * (b - 1), 5625 * (b - 1))[1] * 4 < 1 << 32
+    assert plan([75] * b) < 0 and b"workspace exceeds 4 GB" in lib.gcdm_last_error(h)
+    assert lib.gcdm_num_nodes(h) == 0
+    st, _ = forward()
+    assert st < 0 and b"no batch plan" in lib.gcdm_last_error(h)
+    # the handle plans again
+    assert plan([4, 5]) == 0, lib.gcdm_last_error(h)
+    assert forward() == (0, first)
+    # a packed plan is dropped cleanly
+    per, nn3 = i32([2, 1]), i32([4, 5, 3])
+    assert lib.gcdm_plan_batches(h, 2, ptr(per), ptr(nn3)) == 0, lib.gcdm_last_error(h)
+    assert lib.gcdm_get_option(h, b"num_batches") == 2 and lib.gcdm_num_nodes(h) == 12
+    assert plan([4, 5]) == 0, lib.gcdm_last_error(h)
+    assert lib.gcdm_get_option(h, b"num_batches") == 0 and lib.gcdm_num_nodes(h) == 9
+    assert forward() == (0, first)
+    assert net.read_flags() == 0
 
 
 def _raw_noise(seed, N, F):
