@@ -20,6 +20,7 @@ OPS_LIB_PATH = os.path.join(_HERE, "libgcdm_ops.so")
 OPS_SOURCES = [os.path.join(_HERE, "csrc", "gcdm_ops.hip")]
 OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(_HERE, "csrc", "gcdm_ops.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_ops.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.mp_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_train.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.mp_tile.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_mp_tile.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.gcp2.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_gcp2_train.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.optim.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_optim.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.classifier.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier.h"),
@@ -140,6 +141,13 @@ MP_TRAIN_SIGNATURES = {
     "gcdm_mp_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I32, I32, P],
 }
 MP_TRAIN_RESTYPES = {"gcdm_mp_workspace_bytes": C.c_int64}
+# the same layer on one tile kernel per message GCP, the "tiled" message path (include/gcdm_mp_tile.h): the argument lists of the three above
+MP_TILE_SIGNATURES = {
+    "gcdm_mp_tile_workspace_bytes": [I32, I64, I64, I32, I32],
+    "gcdm_mp_tile_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, I32, I64, I64, I32, I32, P],
+    "gcdm_mp_tile_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I32, I32, P],
+}
+MP_TILE_RESTYPES = {"gcdm_mp_tile_workspace_bytes": C.c_int64}
 
 
 # one stand-alone GCP2 module for training (include/gcdm_gcp2_train.h), exported from the same library
@@ -212,10 +220,10 @@ def load_ops() -> C.CDLL:
     if not os.path.exists(OPS_LIB_PATH):
         raise RuntimeError(f"{OPS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
     lib = C.CDLL(OPS_LIB_PATH)
-    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(GCP2_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(GRAD_BUCKET_SIGNATURES.items()):
+    for name, sig in list(OPS_SIGNATURES.items()) + list(MP_TRAIN_SIGNATURES.items()) + list(MP_TILE_SIGNATURES.items()) + list(GCP2_SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(CLASSIFIER_SIGNATURES.items()) + list(OBJECTIVE_SIGNATURES.items()) + list(GRAD_BUCKET_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = sig
-        fn.restype = {**MP_TRAIN_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
+        fn.restype = {**MP_TRAIN_RESTYPES, **MP_TILE_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
     for name, sig in MATRIX_MODE_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = sig

@@ -1,7 +1,7 @@
 // libgcdm_ops.so -- the module-level operators (forward + backward) behind plug point 3, the non-production configurations and the
 // training objective, the fused message layer and the fused stand-alone GCP2 for training, the fused training update, the EGNN property
 // classifier, the fused diffusion objective, and the flat gradient bucket of data-parallel / accumulated training steps.  One translation unit, independent of libgcdm_hip.so (the fused sampling path); C ABI in
-// include/gcdm_ops.h, include/gcdm_mp_train.h, include/gcdm_gcp2_train.h, include/gcdm_optim.h, include/gcdm_classifier.h,
+// include/gcdm_ops.h, include/gcdm_mp_train.h, include/gcdm_mp_tile.h (the same layer on per-GCP tile kernels), include/gcdm_gcp2_train.h, include/gcdm_optim.h, include/gcdm_classifier.h,
 // include/gcdm_objective.h, include/gcdm_grad_bucket.h and include/gcdm_matrix_mode.h (the fp32 / bf16x6 switch of the GEMM kernels).  gcdm_ops.tile.hip.h comes first:
 // the MFMA tile body, the GEMM launches and the helpers the operator headers share; those depend on it and on gcdm_ops.hip.h's status
 // macros, not on each other.
@@ -11,6 +11,8 @@
 #include "../../include/gcdm_ops.h"
 #include "gcdm_ops.mp_train.hip.h"
 #include "../../include/gcdm_mp_train.h"
+#include "gcdm_ops.mp_tile.hip.h"
+#include "../../include/gcdm_mp_tile.h"
 #include "../../include/gcdm_gcp2_train.h"
 #include "gcdm_ops.gcp2.hip.h"
 #include "../../include/gcdm_optim.h"

@@ -390,6 +390,43 @@ __global__ void k_mp_node_sum(Dims d, const int32_t* __restrict__ rowptr, const 
     }
 }
 
+// ---- backward: every weight gradient of the layer (one grouped split-K launch, one fixed-order slice reduction), from the tape `t` (layout F)
+// and the backward's scratch `ws` (layout L: dspre, gk, dgate, dup, dvh, du, dlog, rscs filled) -- shared by gcdm_mp_bwd and gcdm_mp_tile_bwd ---------
+static inline void wgrad_all(const Dims& d, const FwdLayout& F, const BwdLayout& L, const float* t, float* ws, const float* h, float* dweights,
+                             hipStream_t st, int mode) {
+    const int64_t N = d.N, E = d.E;
+    int64_t sz[NW], off[NW];
+    weight_sizes(d, sz);
+    WgTable T;
+    T.total = wgrad_offsets(sz, NW, off);
+    const float* one = ws + L.one;
+    for (int k = 0; k < 4; ++k) {
+        const int hk = k ? H : d.H0, vin = k ? V : d.VIN0;
+        const float* vpre = k ? t + F.vst[k] : t + F.vpre0;
+        const float* dsp = ws + L.dspre[k];
+        const int64_t ow = off[7 * k + 2];
+        T.add(ws + L.dvh[k], 1, hk, vpre, vin, 1, hk, vin, 3 * E, off[7 * k + 0], vin);                     // dW_down = sum_(e,x) dvh^T v_pre
+        T.add(ws + L.du[k], 1, SV, vpre, vin, 1, SV, vin, 3 * E, off[7 * k + 1], vin);                       // dW_down_frames
+        if (k) {
+            T.add(dsp, 1, S, t + F.x[k], KX, 1, S, KX, E, ow, KX);                                           // dW_s = dS_pre^T X
+        } else {
+            const float* rscs = ws + L.rscs;
+            const float* x0 = t + F.x0;
+            T.add(rscs, 1, 2 * S, h, S, 1, S, S, N, ow, d.KIN0);                                              // W_i: (row sums)^T h
+            T.add(dsp, 1, S, x0, d.K0, 1, S, d.SE, E, ow + S, d.KIN0);                                         // W_e
+            T.add(rscs + S, 1, 2 * S, h, S, 1, S, S, N, ow + S + d.SE, d.KIN0);                                 // W_j: (column sums)^T h
+            T.add(dsp, 1, S, x0 + d.SE, d.K0, 1, S, d.H0 + 3 * SV, E, ow + 2 * S + d.SE, d.KIN0);               // [|vh| | q] columns
+        }
+        T.add(dsp, 1, S, one, 0, 0, S, 1, E, off[7 * k + 3], 1);                                             // b_s
+        T.add(ws + L.dup[k], 1, V, t + F.vh[k], hk, 1, V, hk, 3 * E, off[7 * k + 4], hk);                    // dW_up = sum dup^T vh
+        T.add(ws + L.dgate[k], 1, V, ws + L.gk[k], S, 1, V, S, E, off[7 * k + 5], S);                        // dW_gate = dgate^T silu(S_pre)
+        T.add(ws + L.dgate[k], 1, V, one, 0, 0, V, 1, E, off[7 * k + 6], 1);                                // b_gate
+    }
+    T.add(ws + L.dlog, 0, 1, t + fwd_sfin(F), S, 1, 1, S, E, off[28], S);                                     // attention weight
+    T.add(ws + L.dlog, 0, 1, one, 0, 0, 1, 1, E, off[29], 1);                                                 // attention bias
+    wgrad_launch(T, ws + L.part, dweights, st, mode);
+}
+
 }  // namespace gmp
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -492,37 +529,7 @@ int gcdm_mp_bwd(const float* dagg, const float* h, const int64_t* row, const int
                        ws + L.dvcol, ws + L.rscs, dvnode);
     gemm(ws + L.rscs, 2 * S, 1, t + F.wij, S, 1, dh, nullptr, N, S, 2 * S, st);                    // dh = [RS | CS] . [W_i ; W_j]
 
-    // every weight gradient of the layer: one grouped split-K launch, one fixed-order slice reduction
-    int64_t sz[NW], off[NW];
-    weight_sizes(d, sz);
-    WgTable T;
-    T.total = wgrad_offsets(sz, NW, off);
-    const float* one = ws + L.one;
-    for (int k = 0; k < 4; ++k) {
-        const int hk = k ? H : d.H0, vin = k ? V : d.VIN0;
-        const float* vpre = k ? t + F.vst[k] : t + F.vpre0;
-        const float* dsp = ws + L.dspre[k];
-        const int64_t ow = off[7 * k + 2];
-        T.add(ws + L.dvh[k], 1, hk, vpre, vin, 1, hk, vin, 3 * E, off[7 * k + 0], vin);                     // dW_down = sum_(e,x) dvh^T v_pre
-        T.add(ws + L.du[k], 1, SV, vpre, vin, 1, SV, vin, 3 * E, off[7 * k + 1], vin);                       // dW_down_frames
-        if (k) {
-            T.add(dsp, 1, S, t + F.x[k], KX, 1, S, KX, E, ow, KX);                                           // dW_s = dS_pre^T X
-        } else {
-            const float* rscs = ws + L.rscs;
-            const float* x0 = t + F.x0;
-            T.add(rscs, 1, 2 * S, h, S, 1, S, S, N, ow, d.KIN0);                                              // W_i: (row sums)^T h
-            T.add(dsp, 1, S, x0, d.K0, 1, S, SE, E, ow + S, d.KIN0);                                         // W_e
-            T.add(rscs + S, 1, 2 * S, h, S, 1, S, S, N, ow + S + SE, d.KIN0);                                 // W_j: (column sums)^T h
-            T.add(dsp, 1, S, x0 + SE, d.K0, 1, S, d.H0 + 3 * SV, E, ow + 2 * S + SE, d.KIN0);               // [|vh| | q] columns
-        }
-        T.add(dsp, 1, S, one, 0, 0, S, 1, E, off[7 * k + 3], 1);                                             // b_s
-        T.add(ws + L.dup[k], 1, V, t + F.vh[k], hk, 1, V, hk, 3 * E, off[7 * k + 4], hk);                    // dW_up = sum dup^T vh
-        T.add(ws + L.dgate[k], 1, V, ws + L.gk[k], S, 1, V, S, E, off[7 * k + 5], S);                        // dW_gate = dgate^T silu(S_pre)
-        T.add(ws + L.dgate[k], 1, V, one, 0, 0, V, 1, E, off[7 * k + 6], 1);                                // b_gate
-    }
-    T.add(ws + L.dlog, 0, 1, t + fwd_sfin(F), S, 1, 1, S, E, off[28], S);                                     // attention weight
-    T.add(ws + L.dlog, 0, 1, one, 0, 0, 1, 1, E, off[29], 1);                                                 // attention bias
-    wgrad_launch(T, ws + L.part, dweights, st, mode);
+    wgrad_all(d, F, L, t, ws, h, dweights, st, mode);
     return GOPS_LAUNCH_OK();
 }
 

@@ -487,7 +487,8 @@ class GCPMessagePassing(nn.Module):
         if self.use_scalar_message_attention:
             self.scalar_message_attention = nn.Sequential(nn.Linear(output_dims[0], 1), nn.Sigmoid())
         # Which kernels evaluate forward(): "operators" (default) = the module graph on the HIP operators, any configuration; "fused" = the
-        # whole message function as one autograd node (ops.message_layer), for the configuration why_not_fused() accepts.
+        # whole message function as one autograd node (ops.message_layer), for the configuration why_not_fused() accepts; "tiled" = the same
+        # node on include/gcdm_mp_tile.h's entries (one tile kernel per message GCP), same configuration.
         self.path = "operators"
 
     def why_not_fused(self) -> Optional[str]:
@@ -514,12 +515,12 @@ class GCPMessagePassing(nn.Module):
         return None
 
     def set_path(self, path: str) -> None:
-        if path not in ("operators", "fused"):
-            raise ValueError(f"GCPMessagePassing.path must be 'operators' or 'fused', got {path!r}")
-        if path == "fused":
+        if path not in ("operators", "fused", "tiled"):
+            raise ValueError(f"GCPMessagePassing.path must be 'operators', 'fused' or 'tiled', got {path!r}")
+        if path != "operators":
             why = self.why_not_fused()
             if why is not None:
-                raise NotImplementedError(f"message path 'fused': the fused message layer does not implement this configuration ({why})")
+                raise NotImplementedError(f"message path {path!r}: the fused message layer does not implement this configuration ({why})")
         self.path = path
 
     def fused_weights(self):
@@ -554,15 +555,15 @@ class GCPMessagePassing(nn.Module):
         return ops.scatter_rows(message, ops.graph_of(edge_index, dim_size), self.reduce_function)
 
     def forward(self, node_rep: SV, edge_rep: SV, edge_index: torch.Tensor, frames: torch.Tensor, node_mask: Optional[torch.Tensor] = None) -> SV:
-        if self.path == "fused":
+        if self.path != "operators":
             why = self.why_not_fused()
             if why is not None:
-                raise NotImplementedError(f"message path 'fused': the fused message layer does not implement this configuration ({why})")
+                raise NotImplementedError(f"message path {self.path!r}: the fused message layer does not implement this configuration ({why})")
             edge_mask = None
             if node_mask is not None and not bool(node_mask.all()):          # as _entity_frames: an edge with a masked end point has a zero frame
                 edge_mask = node_mask[edge_index[0]] & node_mask[edge_index[1]]
             return ops.message_layer(node_rep[0], node_rep[1], edge_rep[0], edge_rep[1], frames, ops.graph_of(edge_index, node_rep[0].shape[0]),
-                                     self.fused_weights(), edge_mask=edge_mask)
+                                     self.fused_weights(), edge_mask=edge_mask, path=self.path)
         message = self.message(node_rep, edge_rep, edge_index, frames, node_mask=node_mask)
         return sv_recover(self.aggregate(message, edge_index, dim_size=node_rep[0].shape[0]), self.vector_output_dim)
 

@@ -130,16 +130,17 @@ class GCPNetDynamics(nn.Module):
         return None
 
     def set_message_path(self, path: str) -> None:
-        """"operators" (default) | "fused": how the message function of every interaction layer runs on the module path (training, and any
-        forward_modules call).  "fused" = one autograd node per layer on libgcdm_ops.so's fused message kernels (include/gcdm_mp_train.h);
-        raises NotImplementedError naming the first reason when the configuration is outside what they implement."""
-        if path not in ("operators", "fused"):
-            raise ValueError(f"message path must be 'operators' or 'fused', got {path!r}")
-        if path == "fused":
+        """"operators" (default) | "fused" | "tiled": how the message function of every interaction layer runs on the module path (training,
+        and any forward_modules call).  "fused" = one autograd node per layer on libgcdm_ops.so's fused message kernels
+        (include/gcdm_mp_train.h); "tiled" = the same node on include/gcdm_mp_tile.h's entries (one tile kernel per message GCP, 29 launches
+        per layer instead of 49); both raise NotImplementedError naming the first reason when the configuration is outside what they implement."""
+        if path not in ("operators", "fused", "tiled"):
+            raise ValueError(f"message path must be 'operators', 'fused' or 'tiled', got {path!r}")
+        if path != "operators":
             for layer in self.interaction_layers:
                 why = layer.interaction.why_not_fused()
                 if why is not None:
-                    raise NotImplementedError(f"message path 'fused': the fused message layer does not implement this configuration ({why})")
+                    raise NotImplementedError(f"message path {path!r}: the fused message layer does not implement this configuration ({why})")
         for layer in self.interaction_layers:
             layer.interaction.set_path(path)
 

@@ -548,10 +548,16 @@ MP_EDGE_DIMS = ((64, 16), (16, 8))
 MP_NUM_WEIGHTS = 30
 
 
-def mp_workspace_bytes(which: int, N: int, E: int, SE: int, VE: int) -> int:
-    n = int(_lib().gcdm_mp_workspace_bytes(int(which), int(N), int(E), int(SE), int(VE)))
+MP_PATHS = ("fused", "tiled")          # include/gcdm_mp_train.h | include/gcdm_mp_tile.h (one tile kernel per message GCP): same arguments, same tape
+_MP_ENTRIES = {"fused": ("gcdm_mp_workspace_bytes", "gcdm_mp_fwd", "gcdm_mp_bwd"),
+               "tiled": ("gcdm_mp_tile_workspace_bytes", "gcdm_mp_tile_fwd", "gcdm_mp_tile_bwd")}
+
+
+def mp_workspace_bytes(which: int, N: int, E: int, SE: int, VE: int, path: str = "fused") -> int:
+    name = _MP_ENTRIES[path][0]
+    n = int(getattr(_lib(), name)(int(which), int(N), int(E), int(SE), int(VE)))
     if n < 0:
-        raise ValueError(f"gcdm_mp_workspace_bytes({which}, N={N}, E={E}, SE={SE}, VE={VE}): bad argument")
+        raise ValueError(f"{name}({which}, N={N}, E={E}, SE={SE}, VE={VE}): bad argument")
     return n
 
 
@@ -580,11 +586,13 @@ def _mp_shapes(h, chi, e, xi, frames, graph, weights):
 
 
 class _MessageLayer(torch.autograd.Function):
-    """GCPMessagePassing.forward of the production message configuration: two C calls (gcdm_mp_fwd / gcdm_mp_bwd).  The tape -- what the
-    backward reads -- is one workspace tensor held by the context and dropped by the backward; under no_grad the forward writes none."""
+    """GCPMessagePassing.forward of the production message configuration: two C calls (gcdm_mp_fwd / gcdm_mp_bwd, or the two tiled entries
+    of include/gcdm_mp_tile.h when ``path`` is "tiled").  The tape -- what the backward reads -- is one workspace tensor held by the context
+    and dropped by the backward; under no_grad the forward writes none."""
 
     @staticmethod
-    def forward(ctx, h, chi, e, xi, frames, graph, edge_mask, record, *weights):
+    def forward(ctx, h, chi, e, xi, frames, graph, edge_mask, record, path, *weights):
+        _, fwd_name, _ = _MP_ENTRIES[path]
         SE, VE = _mp_shapes(h, chi, e, xi, frames, graph, weights)
         N, E = graph.N, graph.E
         hs, cs, es, xs = h.detach().contiguous(), chi.detach().contiguous(), e.detach().contiguous(), xi.detach().contiguous()
@@ -595,13 +603,13 @@ class _MessageLayer(torch.autograd.Function):
         alloc = torch.zeros if E == 0 else torch.empty          # no edges: the library writes nothing, the sums are zero
         agg = alloc((N, 256 + 3 * 32), dtype=torch.float32, device=h.device)
         tape = bool(record)                 # (grad mode is off inside forward: the caller says whether a graph is being recorded)
-        ws_t = torch.empty(mp_workspace_bytes(int(tape), N, E, SE, VE) // 4, dtype=torch.float32, device=h.device)
+        ws_t = torch.empty(mp_workspace_bytes(int(tape), N, E, SE, VE, path) // 4, dtype=torch.float32, device=h.device)
         wp = (C.c_void_p * MP_NUM_WEIGHTS)(*[w.data_ptr() for w in ws])
-        _chk(_lib().gcdm_mp_fwd(_p(hs), _p(cs), _p(es), _p(xs), _p(graph.row), _p(graph.col), _p(graph.rowptr), _p(fs), _p(mk), wp, _p(agg), _p(ws_t),
-                                int(tape), N, E, SE, VE, _st(hs)), "gcdm_mp_fwd")
+        _chk(getattr(_lib(), fwd_name)(_p(hs), _p(cs), _p(es), _p(xs), _p(graph.row), _p(graph.col), _p(graph.rowptr), _p(fs), _p(mk), wp, _p(agg),
+                                       _p(ws_t), int(tape), N, E, SE, VE, _st(hs)), fwd_name)
         ctx.tape = ws_t if tape else None
         del ws_t
-        ctx.graph, ctx.frames, ctx.mask, ctx.dims = graph, fs, mk, (N, E, SE, VE)
+        ctx.graph, ctx.frames, ctx.mask, ctx.dims, ctx.path = graph, fs, mk, (N, E, SE, VE), path
         ctx.save_for_backward(hs, *weights)
         ctx.ws = ws
         return agg
@@ -623,11 +631,13 @@ class _MessageLayer(torch.autograd.Function):
         dchi = alloc((N, 32, 3), dtype=torch.float32, device=dev)
         de = alloc((E, SE), dtype=torch.float32, device=dev)
         dxi = alloc((E, VE, 3), dtype=torch.float32, device=dev)
-        dw = alloc(mp_workspace_bytes(3, N, E, SE, VE) // 4, dtype=torch.float32, device=dev)
-        scratch = torch.empty(mp_workspace_bytes(2, N, E, SE, VE) // 4, dtype=torch.float32, device=dev)
+        bwd_name = _MP_ENTRIES[ctx.path][2]
+        dw = alloc(mp_workspace_bytes(3, N, E, SE, VE, ctx.path) // 4, dtype=torch.float32, device=dev)
+        scratch = torch.empty(mp_workspace_bytes(2, N, E, SE, VE, ctx.path) // 4, dtype=torch.float32, device=dev)
         wp = (C.c_void_p * MP_NUM_WEIGHTS)(*[w.data_ptr() for w in ctx.ws])
-        _chk(_lib().gcdm_mp_bwd(_p(g), _p(hs), _p(ctx.graph.row), _p(ctx.graph.col), _p(ctx.graph.rowptr), _p(colptr), _p(colperm), _p(ctx.frames),
-                                _p(ctx.mask), wp, _p(ctx.tape), _p(scratch), _p(dh), _p(dchi), _p(de), _p(dxi), _p(dw), N, E, SE, VE, _st(g)), "gcdm_mp_bwd")
+        _chk(getattr(_lib(), bwd_name)(_p(g), _p(hs), _p(ctx.graph.row), _p(ctx.graph.col), _p(ctx.graph.rowptr), _p(colptr), _p(colperm),
+                                       _p(ctx.frames), _p(ctx.mask), wp, _p(ctx.tape), _p(scratch), _p(dh), _p(dchi), _p(de), _p(dxi), _p(dw), N, E, SE,
+                                       VE, _st(g)), bwd_name)
         ctx.tape = None
         del scratch
         grads, o = [], 0
@@ -637,16 +647,20 @@ class _MessageLayer(torch.autograd.Function):
         ctx.ws = None
         need = ctx.needs_input_grad
         return ((dh if need[0] else None), (dchi if need[1] else None), (de if need[2] else None), (dxi if need[3] else None), None, None, None, None,
-                *[gr if need[8 + i] else None for i, gr in enumerate(grads)])
+                None, *[gr if need[9 + i] else None for i, gr in enumerate(grads)])
 
 
 def message_layer(h: torch.Tensor, chi: torch.Tensor, e: torch.Tensor, xi: torch.Tensor, frames: torch.Tensor, graph: Graph, weights,
-                  edge_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                  edge_mask: Optional[torch.Tensor] = None, path: str = "fused") -> Tuple[torch.Tensor, torch.Tensor]:
     """The message function + sum aggregation of one interaction layer (GCPMessagePassing.forward, production configuration) as one autograd
     node on libgcdm_ops.so's fused kernels.  ``weights``: the 30 tensors in the order of include/gcdm_mp_train.h.  -> (agg_s [N, 256],
-    agg_v [N, 32, 3]).  Raises (no fallback) for shapes, dims or dtypes the kernels do not take; the edge list must be row-sorted (``graph``)."""
+    agg_v [N, 32, 3]).  Raises (no fallback) for shapes, dims or dtypes the kernels do not take; the edge list must be row-sorted (``graph``).
+    ``path``: "fused" (include/gcdm_mp_train.h) or "tiled" (include/gcdm_mp_tile.h: each message GCP's GEMMs and element-wise kernels in one
+    tile kernel, 12 + 17 launches instead of 24 + 25)."""
+    if path not in MP_PATHS:
+        raise ValueError(f"message_layer: path must be one of {MP_PATHS}, got {path!r}")
     record = torch.is_grad_enabled() and any(t.requires_grad for t in (h, chi, e, xi, *weights))
-    agg = _MessageLayer.apply(h, chi, e, xi, frames, graph, edge_mask, record, *weights)
+    agg = _MessageLayer.apply(h, chi, e, xi, frames, graph, edge_mask, record, path, *weights)
     return agg[:, :256], agg[:, 256:].reshape(graph.N, 32, 3)
 
 

@@ -1,13 +1,14 @@
 """Where a training step of the module path spends its time (GPU box): wall clock per step against the GPU-side kernel time of the same steps.
 
-    python tools/train_step_probe.py [steps] [--message-path operators|fused] [--node-path operators|fused] [--matrix-mode f32|bf16x6]   -> wall ms / step, host enqueue ms / step, HIP-event ms / step
+    python tools/train_step_probe.py [steps] [--message-path operators|fused|tiled] [--node-path operators|fused] [--matrix-mode f32|bf16x6]   -> wall ms / step, host enqueue ms / step, HIP-event ms / step
     rocprofv3 --kernel-trace --stats -- python tools/train_step_probe.py 5      (sum of kernel durations / steps = GPU busy time per step)
 
 --update torch|fused adds the update after backward(): `torch` the reference's recipe in stock torch (adaptive clipping with two host
 syncs, AdamW amsgrad, the per-entry EMA), `fused` optim.TrainingUpdate (three launches); the default `none` is the bare forward + backward.
 
 --message-path fused runs every interaction layer's message function as one autograd node on the fused message kernels
-(GCPNetDynamics.set_message_path, include/gcdm_mp_train.h); the default is the operator path bench.py times.
+(GCPNetDynamics.set_message_path, include/gcdm_mp_train.h), --message-path tiled the same node on one tile kernel per message GCP
+(include/gcdm_mp_tile.h: 29 launches per layer instead of 49); the default is the operator path bench.py times.
 
 --node-path fused runs every stand-alone GCP2 (the embedding GCPs, the feed-forward and position GCPs of each layer, the scalar projection) as
 one autograd node on the fused GCP2 kernels (GCPNetDynamics.set_node_path, include/gcdm_gcp2_train.h); independent of --message-path.
@@ -106,7 +107,7 @@ def main():
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("steps", nargs="?", type=int, default=10)
-    ap.add_argument("--message-path", choices=("operators", "fused"), default="operators")
+    ap.add_argument("--message-path", choices=("operators", "fused", "tiled"), default="operators")
     ap.add_argument("--node-path", choices=("operators", "fused"), default="operators")
     ap.add_argument("--objective-path", choices=("operators", "fused"), default="operators")
     ap.add_argument("--update", choices=("none", "torch", "fused"), default="none")
