@@ -22,6 +22,8 @@ from . import optim                                                             
 from .optim import TrainingUpdate, BucketedUpdate                                # noqa: F401
 from . import classifier                                                         # noqa: F401
 from .classifier import EGNN, get_classifier, property_mae                       # noqa: F401
+from . import data                                                               # noqa: F401
+from .data import MoleculeDataset, DeviceLoader, PropertiesDistribution          # noqa: F401
 from .sdf import write_sdf_file, build_molecules, bond_order_matrices, Molecule  # noqa: F401
 from .xyz import save_xyz_file, write_xyz_file                                  # noqa: F401
 from .stability import check_molecular_stability, check_molecular_stability_batch, get_bond_length_arrays, CategoricalDistribution  # noqa: F401
@@ -34,4 +36,5 @@ __all__ = [
     "check_molecular_stability", "check_molecular_stability_batch", "get_bond_length_arrays", "CategoricalDistribution",
     "save_xyz_file", "write_xyz_file", "write_sdf_file", "build_molecules", "bond_order_matrices", "Molecule", "F16RangeError",
     "optim", "TrainingUpdate", "BucketedUpdate", "classifier", "EGNN", "get_classifier", "property_mae",
+    "data", "MoleculeDataset", "DeviceLoader", "PropertiesDistribution",
 ]

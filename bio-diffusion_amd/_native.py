@@ -26,6 +26,7 @@ OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(
                os.path.join(_HERE, "csrc", "gcdm_ops.classifier.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.objective.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_objective.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.bucket.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_grad_bucket.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.data.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_data.h"),
                os.path.join(os.path.dirname(_HERE), "include", "gcdm_matrix_mode.h")]
 ABI_VERSION = 2
 
@@ -209,6 +210,28 @@ MATRIX_MODE_SIGNATURES = {
 }
 MATRIX_MODE_RESTYPES = {"gcdm_ops_get_matrix_mode": C.c_int32}
 MATRIX_MODES = {"f32": 0, "bf16x6": 1}          # GCDM_OPS_MATRIX_F32, GCDM_OPS_MATRIX_BF16X6
+
+
+# the device-resident molecule data set: collation, property histograms, context draws (include/gcdm_data.h), exported from the same library
+class DataSet(C.Structure):
+    _fields_ = [("atom_ptr", P), ("z", P), ("pos", P), ("props", P), ("species", P), ("norm", P), ("index", P), ("M", I64), ("A", I64),
+                ("P", I32), ("T", I32)]
+
+
+class DataBatch(C.Structure):
+    _fields_ = [(name, P) for name in ("x", "one_hot", "charges", "batch", "mask", "index", "num_nodes_present", "props", "props_context",
+                                       "edge_index", "rowptr", "colperm", "colptr")]
+
+
+DATA_SIGNATURES = {
+    "gcdm_data_workspace_bytes": [I64],
+    "gcdm_data_collate": [C.POINTER(DataSet), P, I64, I64, I64, I32, P, I32, I64, I64, P, C.POINTER(DataBatch), P, P],
+    "gcdm_data_prop_histogram": [P, P, I64, I32, I32, P, P, P, P, P],
+    "gcdm_data_prop_sample": [P, P, P, P, P, P, I64, I32, I32, I32, P, P, P],
+}
+DATA_RESTYPES = {"gcdm_data_workspace_bytes": C.c_int64}
+DATA_MAX_TYPES, DATA_MAX_PROPS, DATA_MAX_SIZES, DATA_MAX_BINS = 16, 32, 2048, 65536          # GCDM_DATA_MAX_*
+DATA_FLAG_ABSENT_SIZE, DATA_FLAG_ACCOUNT = 1, 2                                               # GCDM_DATA_FLAG_*
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -224,10 +247,11 @@ def load_ops() -> C.CDLL:
         fn = getattr(lib, name)
         fn.argtypes = sig
         fn.restype = {**MP_TRAIN_RESTYPES, **MP_TILE_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
-    for name, sig in MATRIX_MODE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = sig
-        fn.restype = MATRIX_MODE_RESTYPES.get(name, C.c_int)
+    for table, restypes in ((MATRIX_MODE_SIGNATURES, MATRIX_MODE_RESTYPES), (DATA_SIGNATURES, DATA_RESTYPES)):
+        for name, sig in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes = sig
+            fn.restype = restypes.get(name, C.c_int)
     _ops_lib = lib
     return lib
 

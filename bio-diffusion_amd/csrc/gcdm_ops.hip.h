@@ -181,7 +181,8 @@ __global__ void k_segment_bwd(const float* __restrict__ dout, const int64_t* __r
     if (mean) { const int cnt = rowptr[n + 1] - rowptr[n]; g /= (float)(cnt > 1 ? cnt : 1); }
     dx[i] = g;
 }
-// backward of a gather by an UNSORTED index (the column index of an edge list): fp32 atomics, summation order not fixed
+// backward of a gather by an UNSORTED index (ops.embedding's table gradient): fp32 atomics, summation order not fixed.  (The gather by an edge
+// list's column index is summed in the graph's column order instead: gcdm_op_gather + gcdm_op_segment_sum, ops.py)
 __global__ void k_scatter_add(const float* __restrict__ dy, const int64_t* __restrict__ idx, float* __restrict__ out, int64_t E, int C) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= E * C) return;

@@ -1,0 +1,370 @@
+"""Device-resident molecule data sets: the whole processed QM9 / GEOM split lives in HBM and a training batch is built from it by two launches
+(include/gcdm_data.h), with no host round trip.
+
+What it replaces in the reference (BioinfoMachineLearning/bio-diffusion): ``ProcessedDataset`` + the PyG ``DataLoader`` of
+``EDMDataModule.train_dataloader()`` (src/datamodules/components/edm_dataset.py:79-226), ``prepare_context``
+(src/datamodules/components/edm/utils.py:333-382), ``compute_mean_mad_from_dataloader`` and ``PropertiesDistribution``
+(src/models/__init__.py:63-76, 311-415).  A batch also carries what the network would otherwise rebuild from it with device-to-host copies:
+the fully connected graph with its CSR (``fc_graph``), ``all_present`` and ``num_graphs``.
+
+Out of scope: downloading or pre-processing raw QM9 / GEOM, ``remove_h``, GEOM's same-size ``CustomBatchSampler`` (``sequential``),
+overlapping the collation with the previous step on a side stream, Lightning.  There is no CPU path: the data set lives on an MI355X.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Any, Dict, Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _native, ops
+from .config import AttrDict
+
+_NOT_PROPERTIES = ("num_atoms", "charges", "positions", "index", "one_hot", "atom_mask")          # edm_dataset.py:206
+
+
+def _lib():
+    return _native.load_ops()
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream(device) -> C.c_void_p:
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _chk(status: int, what: str) -> None:
+    if status != 0:
+        raise _native.NativeError(f"{what} failed with status {status} (libgcdm_ops.so)")
+
+
+def _cpu(v: Any) -> torch.Tensor:
+    return v.detach().cpu() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+
+
+def distributed_indices(length: int, shuffle: bool, seed: int, epoch: int, rank: int, world: int) -> torch.Tensor:
+    """The index stream of ``torch.utils.data.DistributedSampler(range(length), world, rank, shuffle, seed)`` after ``set_epoch(epoch)``:
+    ``randperm`` from a CPU generator seeded ``seed + epoch``, padded by wrap-around to a multiple of ``world``, then ``[rank::world]``."""
+    if not (0 <= rank < world):
+        raise ValueError(f"rank {rank} outside [0, {world})")
+    if shuffle:
+        g = torch.Generator()
+        g.manual_seed(int(seed) + int(epoch))
+        idx = torch.randperm(length, generator=g)
+    else:
+        idx = torch.arange(length)
+    total = math.ceil(length / world) * world
+    pad = total - length
+    if pad > 0 and length > 0:
+        idx = torch.cat([idx] + [idx] * math.ceil(pad / length))[:total]
+    return idx[rank:total:world].contiguous()
+
+
+def batch_accounting(sizes: np.ndarray, pad_to: int):
+    """(N, E, all_present) of a batch of molecules with ``sizes`` atoms: rows and edges (all ordered pairs, self-loops included)."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    N = int(len(sizes) * pad_to) if pad_to > 0 else int(sizes.sum())
+    return N, int((sizes * sizes).sum()), bool(pad_to == 0 or (sizes == pad_to).all())
+
+
+class MoleculeDataset:
+    """The reference's processed dictionary (``num_atoms [M]``, ``charges [M, A_max]``, ``positions [M, A_max, 3]``, optional ``index``, 1-D
+    property arrays, ``<key>_thermo`` companions) after ProcessedDataset's filters, uploaded once in a ragged layout; the sizes stay mirrored on
+    the host.  ``num_pts`` limits what a loader iterates to the first ``num_pts`` molecules (statistics and histograms see all, as in the
+    reference); ``filter_n_atoms`` keeps molecules of that many atoms (edm/dataset.py:114-123; ``stats`` is computed before it, as there).
+    ``conditioning``: the property keys whose normalised per-node copies make ``props_context``."""
+
+    def __init__(self, data: Dict[str, Any], device, included_species=None, subtract_thermo: bool = True, remove_zero_charge_molecules: bool = True,
+                 num_pts: int = -1, filter_n_atoms: Optional[int] = None, conditioning: Sequence[str] = ()):
+        data = {k: _cpu(v) for k, v in data.items()}
+        for key in ("num_atoms", "charges", "positions"):
+            if key not in data:
+                raise KeyError(f"the processed dictionary has no {key!r}")
+        M0 = data["charges"].shape[0]
+        if "index" not in data:
+            data["index"] = torch.arange(M0, dtype=torch.int64)
+        if remove_zero_charge_molecules:
+            keep = data["charges"].sum(-1) > 0
+            data = {k: v[keep] for k, v in data.items()}
+        if included_species is None:
+            included_species = torch.unique(data["charges"], sorted=True)
+            if len(included_species) and included_species[0] == 0:
+                included_species = included_species[1:]
+        included_species = torch.as_tensor(included_species).reshape(-1).to(torch.int32)
+        if subtract_thermo:
+            for key in [k.split("_")[0] for k in data if k.endswith("_thermo")]:
+                data[key] = data[key] - data[key + "_thermo"].to(data[key].dtype)
+        self.stats = {k: (v.mean(), v.std()) for k, v in data.items() if v.dim() == 1 and v.is_floating_point()}          # calc_stats
+        if filter_n_atoms is not None:
+            keep = data["num_atoms"] == int(filter_n_atoms)
+            data = {k: v[keep] for k, v in data.items()}
+        charges = data["charges"].to(torch.int64)
+        present = charges > 0
+        n = present.sum(-1)
+        if bool((present != (torch.arange(charges.shape[1]).unsqueeze(0) < n.unsqueeze(1))).any()):
+            raise ValueError("a molecule has a zero charge in front of a non-zero one: the reference keeps such a row in place, this layout compacts "
+                             "the present atoms to the front of the molecule")
+        if bool((n != data["num_atoms"].to(torch.int64)).any()):
+            raise ValueError("num_atoms differs from the number of non-zero charges of a molecule")
+        props = {k: v for k, v in data.items() if k not in _NOT_PROPERTIES and v.dim() == 1 and v.shape[0] == charges.shape[0]}
+        self._init_ragged(n, charges[present].to(torch.int32), data["positions"][present].to(torch.float32), props, data["index"].to(torch.int64),
+                          included_species, device, num_pts, conditioning, max_atoms=int(charges.shape[1]))
+
+    def _init_ragged(self, n, z, pos, props, index, included_species, device, num_pts, conditioning, max_atoms):
+        self.device = torch.device(device)          # "cpu" prepares, filters and takes statistics only: batches and histograms need the GPU
+        M = int(n.shape[0])
+        if len(props) > _native.DATA_MAX_PROPS or len(included_species) > _native.DATA_MAX_TYPES:
+            raise ValueError(f"at most {_native.DATA_MAX_PROPS} properties and {_native.DATA_MAX_TYPES} species")
+        self.M, self.max_atoms = M, int(max_atoms)
+        self.num_pts = M if num_pts is None or num_pts < 0 else min(int(num_pts), M)
+        self.included_species = included_species
+        self.num_species, self.max_charge = len(included_species), (int(included_species.max()) if len(included_species) else 0)
+        self.parameters = {"num_species": self.num_species, "max_charge": self.max_charge}
+        self.property_keys = list(props)
+        self.conditioning = list(conditioning)
+        for key in self.conditioning:
+            if key not in props:
+                raise KeyError(f"conditioning on {key!r}: the data has no such property (it has {self.property_keys})")
+        self.data = dict(props)                                        # the host copies, in the data's own dtype (statistics are taken on these)
+        self.data["num_atoms"] = n.clone()
+        self.num_atoms_host = n.numpy().astype(np.int64)                # the host mirror of the sizes
+        atom_ptr = torch.zeros(M + 1, dtype=torch.int64)
+        atom_ptr[1:] = torch.cumsum(n, 0)
+        self.A = int(atom_ptr[-1])
+        norms = self.mean_mad(self.property_keys)
+        dev = self.device
+        self.atom_ptr, self.z, self.pos, self.index = atom_ptr.to(dev), z.contiguous().to(dev), pos.contiguous().to(dev), index.contiguous().to(dev)
+        P = len(props)
+        self.props = (torch.stack([v.to(torch.float32) for v in props.values()]) if P else torch.zeros(0, M)).contiguous().to(dev)
+        self.norm = (torch.tensor([[float(norms[k]["mean"].to(torch.float32)), float(norms[k]["mad"].to(torch.float32))] for k in props],
+                                  dtype=torch.float32).reshape(P, 2)).to(dev)
+        self.species = included_species.contiguous().to(dev)
+        self.ctx_cols = torch.tensor([self.property_keys.index(k) for k in self.conditioning], dtype=torch.int32).to(dev)
+        self.flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._z_host = z
+        self._set = _native.DataSet(self.atom_ptr.data_ptr(), self.z.data_ptr(), self.pos.data_ptr(), self.props.data_ptr(), self.species.data_ptr(),
+                                    self.norm.data_ptr(), self.index.data_ptr(), M, self.A, P, self.num_species)
+
+    @classmethod
+    def from_npz(cls, path: str, device, **kw) -> "MoleculeDataset":
+        """The reference's ``train.npz`` / ``valid.npz`` / ``test.npz`` (edm/utils.py:175-180)."""
+        with np.load(path) as f:
+            return cls({k: torch.from_numpy(np.asarray(f[k])) for k in f.files}, device, **kw)
+
+    @classmethod
+    def from_conformers(cls, conformers: Iterable[Any], device, properties: Optional[Dict[str, Any]] = None, included_species=None,
+                        num_pts: int = -1, conditioning: Sequence[str] = ()) -> "MoleculeDataset":
+        """GEOM's layout: one ``[n, 4]`` array (atomic number, x, y, z) per conformer, never padded on the host."""
+        confs = [torch.as_tensor(np.asarray(c), dtype=torch.float32).reshape(-1, 4) for c in conformers]
+        n = torch.tensor([c.shape[0] for c in confs], dtype=torch.int64)
+        flat = torch.cat(confs) if confs else torch.zeros(0, 4)
+        z = flat[:, 0].to(torch.int32)
+        if bool((z <= 0).any()) or bool((n == 0).any()):
+            raise ValueError("a conformer holds an atom with atomic number <= 0, or no atom at all")
+        if included_species is None:
+            included_species = torch.unique(z, sorted=True)
+        props = {k: _cpu(v) for k, v in (properties or {}).items()}
+        self = cls.__new__(cls)
+        self.stats = {k: (v.mean(), v.std()) for k, v in props.items() if v.is_floating_point()}
+        self._init_ragged(n, z, flat[:, 1:4].contiguous(), props, torch.arange(len(confs), dtype=torch.int64),
+                          torch.as_tensor(included_species).reshape(-1).to(torch.int32), device, num_pts, conditioning,
+                          max_atoms=int(n.max()) if len(confs) else 0)
+        return self
+
+    def __len__(self) -> int:
+        return self.num_pts
+
+    def mean_mad(self, properties: Sequence[str]) -> Dict[str, Dict[str, torch.Tensor]]:
+        """compute_mean_mad_from_dataloader (src/models/__init__.py:63-76) on the data set's own values."""
+        out = {}
+        for key in properties:
+            v = self.data[key]
+            v = v if v.is_floating_point() else v.to(torch.float32)
+            mean = torch.mean(v)
+            out[key] = {"mean": mean, "mad": torch.mean(torch.abs(v - mean))}
+        return out
+
+    def n_nodes_histogram(self) -> Dict[int, int]:
+        """{size: molecules} in ascending size: what NumNodesDistribution takes."""
+        sizes, counts = np.unique(self.num_atoms_host, return_counts=True)
+        return {int(s): int(c) for s, c in zip(sizes, counts)}
+
+    def atom_type_histogram(self) -> Dict[int, int]:
+        """{one-hot column: atoms}, the ``atom_types`` entry of a dataset_info."""
+        zs = self._z_host.to(torch.int64)
+        return {t: int((zs == int(s)).sum()) for t, s in enumerate(self.included_species)}
+
+    def loader(self, batch_size: int, shuffle: bool = True, drop_last: bool = False, seed: int = 0, layout: str = "padded", rank: int = 0,
+               world: int = 1) -> "DeviceLoader":
+        return DeviceLoader(self, batch_size, shuffle, drop_last, seed, layout, rank, world)
+
+    def collate(self, perm: torch.Tensor, first: int, B: int, pad_to: int, sizes: np.ndarray) -> AttrDict:
+        """One batch of molecules ``perm[first : first + B]`` (``perm`` int64 on the device, ``sizes`` their atom counts from the host mirror):
+        two launches on the current stream, no device-to-host copy."""
+        ops._dev(self.atom_ptr)
+        N, E, all_present = batch_accounting(sizes, pad_to)
+        dev, P, T, Cn = self.device, len(self.property_keys), self.num_species, len(self.conditioning)
+        f32 = dict(dtype=torch.float32, device=dev)
+        i64 = dict(dtype=torch.int64, device=dev)
+        x, one_hot, charges = torch.empty((N, 3), **f32), torch.empty((N, T), **f32), torch.empty((N, 1), **f32)
+        bi, mask = torch.empty(N, **i64), torch.empty(N, dtype=torch.bool, device=dev)
+        index, present, props = torch.empty(B, **i64), torch.empty(B, **i64), torch.empty((P, B), **f32)
+        ctx = torch.empty((N, Cn), **f32) if Cn else None
+        edge_index, colperm = torch.empty((2, E), **i64), torch.empty(E, **i64)
+        rowptr, colptr = torch.empty(N + 1, dtype=torch.int32, device=dev), torch.empty(N + 1, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(_lib().gcdm_data_workspace_bytes(B)), dtype=torch.uint8, device=dev)
+        out = _native.DataBatch(*[None if t is None else t.data_ptr() for t in (x, one_hot, charges, bi, mask, index, present, props, ctx, edge_index,
+                                                                                rowptr, colperm, colptr)])
+        _chk(_lib().gcdm_data_collate(C.byref(self._set), _ptr(perm), int(perm.shape[0]), int(first), int(B), int(pad_to), _ptr(self.ctx_cols), Cn,
+                                      N, E, _ptr(ws), C.byref(out), _ptr(self.flags), _stream(dev)), "gcdm_data_collate")
+        # charges leaves as [N], the shape of the reference's batches (its items' [A_max] rows concatenated), which normalize() multiplies by the mask
+        batch = AttrDict(x=x, one_hot=one_hot, charges=charges.reshape(N), batch=bi, mask=mask, index=index, num_graphs=int(B), num_nodes_present=present,
+                         all_present=all_present)
+        for p, key in enumerate(self.property_keys):
+            batch[key] = props[p]
+        if Cn:
+            batch["props_context"] = ctx
+        batch["fc_graph"] = ops.Graph.from_parts(edge_index, N, rowptr, colperm, colptr)
+        return batch
+
+    def check(self) -> None:
+        """Reads the device flag word (one device-to-host copy; not part of iterating): raises if a collation's sizes did not add up."""
+        f = int(self.flags.item())
+        if f & _native.DATA_FLAG_ACCOUNT:
+            raise RuntimeError("a batch's sizes on the device did not add up to the host mirror's N and E (or an index was out of range): the batch "
+                               "is not to be used")
+
+
+class DeviceLoader:
+    """Iterates a MoleculeDataset in batches; ``set_epoch(e)`` as on a DistributedSampler.  The index stream is
+    ``distributed_indices(len(dataset), shuffle, seed, epoch, rank, world)``, uploaded once per epoch; ``drop_last`` drops a short last batch.
+    ``layout="padded"``: every molecule takes ``dataset.max_atoms`` rows (the reference's batches); ``"compact"``: present atoms only."""
+
+    def __init__(self, dataset: MoleculeDataset, batch_size: int, shuffle: bool = True, drop_last: bool = False, seed: int = 0, layout: str = "padded",
+                 rank: int = 0, world: int = 1):
+        if layout not in ("padded", "compact"):
+            raise ValueError(f"layout must be 'padded' or 'compact', got {layout!r}")
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size = {batch_size}")
+        self.dataset, self.batch_size, self.shuffle, self.drop_last = dataset, int(batch_size), bool(shuffle), bool(drop_last)
+        self.seed, self.layout, self.rank, self.world = int(seed), layout, int(rank), int(world)
+        self.pad_to = dataset.max_atoms if layout == "padded" else 0
+        self.epoch, self._perm_epoch = 0, None
+        self.indices = distributed_indices(len(dataset), self.shuffle, self.seed, 0, self.rank, self.world)
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def __len__(self) -> int:
+        n = len(self.indices)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _upload(self) -> None:
+        if self._perm_epoch != self.epoch:
+            self.indices = distributed_indices(len(self.dataset), self.shuffle, self.seed, self.epoch, self.rank, self.world)
+            self._sizes = self.dataset.num_atoms_host[self.indices.numpy()]
+            self._perm = self.indices.to(self.dataset.device)
+            self._perm_epoch = self.epoch
+
+    def __iter__(self):
+        self._upload()
+        self._cursor = 0
+        return self
+
+    def __next__(self) -> AttrDict:
+        first, n = self._cursor, len(self.indices)
+        B = min(self.batch_size, n - first)
+        if B <= 0 or (self.drop_last and B < self.batch_size):
+            raise StopIteration
+        self._cursor = first + B
+        return self.dataset.collate(self._perm, first, B, self.pad_to, self._sizes[first:first + B])
+
+
+class PropertiesDistribution:
+    """The reference's PropertiesDistribution (src/models/__init__.py:311-415) on the device: per property and molecule size the integer
+    histogram of ``num_bins`` bins over [min, max], built by one launch per property; ``sample_batch`` draws a normalised context ``[B, P]`` by
+    one launch, from ``torch.rand`` on the device (seedable through ``generator``).  ``distributions[prop][n]`` holds ``params`` (min, max)
+    and ``counts``.  A size without members makes ``sample_batch`` raise KeyError: at once for host sizes, at the next ``check()`` or call for
+    sizes given on the device (their rows are NaN)."""
+
+    def __init__(self, dataset: MoleculeDataset, properties: Sequence[str], num_bins: int = 1000, normalizer: Optional[Dict[str, Dict[str, Any]]] = None):
+        self.dataset, self.properties, self.num_bins, self.device = dataset, list(properties), int(num_bins), dataset.device
+        if not 1 <= self.num_bins <= _native.DATA_MAX_BINS:
+            raise ValueError(f"num_bins must be 1 .. {_native.DATA_MAX_BINS}")
+        ops._dev(dataset.atom_ptr)
+        S =int(dataset.num_atoms_host.max()) + 1 if dataset.M else 0
+        if S > _native.DATA_MAX_SIZES:
+            raise ValueError(f"molecules of up to {_native.DATA_MAX_SIZES - 1} atoms")
+        Pn, dev = len(self.properties), self.device
+        self.num_sizes = S
+        self.counts = torch.empty((Pn, S, self.num_bins), dtype=torch.int32, device=dev)
+        self.params = torch.empty((Pn, S, 2), dtype=torch.float32, device=dev)
+        self.members = torch.empty((Pn, S), dtype=torch.int32, device=dev)
+        self.flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        for p, key in enumerate(self.properties):
+            row = dataset.props[dataset.property_keys.index(key)]
+            _chk(_lib().gcdm_data_prop_histogram(_ptr(dataset.atom_ptr), _ptr(row), dataset.M, S, self.num_bins, _ptr(self.counts[p]),
+                                                 _ptr(self.params[p]), _ptr(self.members[p]), _ptr(self.flags), _stream(dev)),
+                 "gcdm_data_prop_histogram")
+        params, members, counts = self.params.cpu(), self.members.cpu(), self.counts.cpu()          # once, at construction
+        if int(self.flags.item()) & _native.DATA_FLAG_ACCOUNT:
+            raise RuntimeError("gcdm_data_prop_histogram: a molecule's size is outside the tables")
+        self._members_host = members.numpy()
+        self.distributions = {key: {n: {"params": (params[p, n, 0], params[p, n, 1]), "counts": counts[p, n]}
+                                    for n in range(S) if int(members[p, n]) > 0} for p, key in enumerate(self.properties)}
+        self._flags_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._event = None
+        self.normalizer = None
+        if normalizer is not None:
+            self.set_normalizer(normalizer)
+
+    def set_normalizer(self, normalizer: Dict[str, Dict[str, Any]]) -> None:
+        self.normalizer = normalizer
+        self._norm = torch.tensor([[float(torch.as_tensor(normalizer[k]["mean"]).to(torch.float32)),
+                                    float(torch.as_tensor(normalizer[k]["mad"]).to(torch.float32))] for k in self.properties],
+                                  dtype=torch.float32).reshape(len(self.properties), 2).to(self.device)
+
+    def check(self, wait: bool = True) -> None:
+        """Raises KeyError if an earlier ``sample_batch`` met a size without members.  ``wait=False`` looks only if the copy has arrived."""
+        if self._event is None or (not wait and not self._event.query()):
+            return
+        self._event.synchronize()
+        self._event = None
+        if int(self._flags_host[0]) & _native.DATA_FLAG_ABSENT_SIZE:
+            self._flags_host.zero_()
+            self.flags.zero_()
+            raise KeyError("PropertiesDistribution.sample_batch: a requested molecule size has no member in the data set")
+
+    def sample_batch(self, num_nodes: torch.Tensor, generator: Optional[torch.Generator] = None, u: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Normalised context ``[B, P]`` on the device.  ``u`` ``[B, P, 2]`` replaces the uniforms (tests)."""
+        if self.normalizer is None:
+            raise AssertionError("To normalize properties, `normalizer` must not be null.")
+        self.check(wait=False)
+        num_nodes = torch.as_tensor(num_nodes)
+        B, Pn, dev = int(num_nodes.numel()), len(self.properties), self.device
+        if num_nodes.device.type == "cpu":
+            nn_host = num_nodes.reshape(-1).to(torch.int64).numpy()
+            for n in nn_host:
+                if not (0 <= n < self.num_sizes) or (Pn and self._members_host[0, n] <= 0):
+                    raise KeyError(int(n))
+        nn_dev = num_nodes.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        if u is None:
+            u = torch.rand((B, Pn, 2), dtype=torch.float32, device=dev, generator=generator)
+        u = u.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(u.shape) != (B, Pn, 2):
+            raise ValueError(f"u {tuple(u.shape)} must be [{B}, {Pn}, 2]")
+        out = torch.empty((B, Pn), dtype=torch.float32, device=dev)
+        _chk(_lib().gcdm_data_prop_sample(_ptr(self.counts), _ptr(self.params), _ptr(self.members), _ptr(self._norm), _ptr(nn_dev), _ptr(u), B, Pn,
+                                          self.num_sizes, self.num_bins, _ptr(out), _ptr(self.flags), _stream(dev)), "gcdm_data_prop_sample")
+        if num_nodes.device.type != "cpu":                      # the host could not look: the flag word follows without blocking
+            self._flags_host.copy_(self.flags, non_blocking=True)
+            self._event = torch.cuda.Event()
+            self._event.record(torch.cuda.current_stream(dev))
+        return out
+
+    def sample(self, num_nodes: int = 19) -> torch.Tensor:
+        return self.sample_batch(torch.tensor([int(num_nodes)]))[0]

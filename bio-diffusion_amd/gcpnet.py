@@ -214,11 +214,18 @@ class GCPNetDynamics(nn.Module):
         xh = xh.to(torch.float32) * mf
         x_init, h = xh[:, :nx].contiguous(), xh[:, nx:]
         N = xh.shape[0]
-        counts = torch.unique_consecutive(bi, return_counts=True)[1]
-        edge_index = ops.fully_connected_edge_index(counts.cpu(), xh.device)
-        full_mask = bool(mask.all())
-        if not full_mask:                                        # edges of masked nodes do not exist (gcpnet.py:1062-1065)
-            edge_index = edge_index[:, mask[edge_index[0]] & mask[edge_index[1]]].contiguous()
+        fc_graph = cfg_get(batch, "fc_graph")
+        if isinstance(fc_graph, ops.Graph) and getattr(fc_graph, "edge_index", None) is not None and fc_graph.N == N \
+                and cfg_get(batch, "all_present") is not None:
+            # a data loader's batch (data.py) brings the graph ready-made: no device-to-host copy, no checking launch
+            edge_index, full_mask = fc_graph.edge_index, bool(cfg_get(batch, "all_present"))
+            ops.register_graph(fc_graph, edge_index)
+        else:
+            counts = torch.unique_consecutive(bi, return_counts=True)[1]
+            edge_index = ops.fully_connected_edge_index(counts.cpu(), xh.device)
+            full_mask = bool(mask.all())
+            if not full_mask:                                        # edges of masked nodes do not exist (gcpnet.py:1062-1065)
+                edge_index = edge_index[:, mask[edge_index[0]] & mask[edge_index[1]]].contiguous()
         chi = ops.orientations(x_init)
         e, xi = ops.edge_features(x_init, edge_index)
         if self.self_condition:

@@ -119,7 +119,7 @@ class _MoleculeGenerationDDPM(nn.Module):
                                           diffusion_cfg=diffusion_cfg, dataloader_cfg=dataloader_cfg)
         self.ddpm = EquivariantVariationalDiffusion(dynamics_network=dynamics_network, diffusion_cfg=diffusion_cfg,
                                                     dataloader_cfg=dataloader_cfg, dataset_info=self.dataset_info)
-        self.props_distr = None   # set by the conditional-evaluation driver (PropertiesDistribution needs training data)
+        self.props_distr = None   # PropertiesDistribution needs training data: attach_dataset(data.MoleculeDataset) sets it
         # qm9_mol_gen_ddpm.py:196-199: node-type statistics of the training set, for the KL reported by analyze_samples
         self.node_type_distribution = CategoricalDistribution(self.dataset_info["atom_types"], self.dataset_info["atom_encoder"])
         self.molecular_metrics = None   # BasicMolecularMetrics needs RDKit + the training SMILES (out of scope); attach one to get validity etc.
@@ -129,6 +129,17 @@ class _MoleculeGenerationDDPM(nn.Module):
     @property
     def device(self) -> torch.device:
         return next(self.parameters()).device
+
+    def attach_dataset(self, dataset: Any, properties: Optional[List[str]] = None, num_bins: int = 1000):
+        """Sets ``props_distr`` from a device-resident training set (data.MoleculeDataset): the reference's PropertiesDistribution over
+        ``properties`` (default: the data set's ``conditioning``), normalised with the data set's own mean / mad -- what the reference's
+        training script builds from ``train_dataloader()``.  Returns it."""
+        from .data import PropertiesDistribution
+        props = list(dataset.conditioning if properties is None else properties)
+        if not props:
+            raise ValueError("attach_dataset: no properties to condition on (the data set was built without `conditioning`)")
+        self.props_distr = PropertiesDistribution(dataset, props, num_bins=num_bins, normalizer=dataset.mean_mad(props))
+        return self.props_distr
 
     # the reference calls ``model.load_from_checkpoint(...)`` on an instance (mol_gen_sample.py:113-122)
     def load_from_checkpoint(self, checkpoint_path: str, map_location: Any = None, strict: bool = True, **kwargs):
@@ -151,8 +162,8 @@ class _MoleculeGenerationDDPM(nn.Module):
         """Loss per molecule and the batch means of the monitored terms.  Evaluation mode: the NLL (two evaluations of the network, fused
         kernels, inference mode).  Training mode: the L2 or VLB objective of ``diffusion_cfg.loss_type`` with gradients -- the network runs on
         the module path (HIP operators with autograd).  ``batch``: x, one_hot, charges, batch, mask and -- for a conditional model -- the
-        per-node ``props_context`` (the reference derives it from the training set's property statistics, qm9utils.prepare_context; that data
-        path is outside this package).  ``t_int`` / ``noise`` / ``self_conditioning_prob``: see EquivariantVariationalDiffusion.forward."""
+        per-node ``props_context`` (the reference derives it from the training set's property statistics, qm9utils.prepare_context; a
+        batch of data.MoleculeDataset's loader carries it).  ``t_int`` / ``noise`` / ``self_conditioning_prob``: see EquivariantVariationalDiffusion.forward."""
         if self.training:
             return self._forward_impl(batch, dtype, t_int, noise, self_conditioning_prob)
         with torch.inference_mode():
@@ -192,7 +203,8 @@ class _MoleculeGenerationDDPM(nn.Module):
         if self.ddpm.objective_path == "fused":
             return self._forward_fused(batch, dtype, t_int, noise, self_conditioning_prob)
         bi, mask = batch.batch, batch.mask
-        B = int(bi.max().item()) + 1
+        B = getattr(batch, "num_graphs", None)                                  # a data loader's batch (data.py) brings it: no device-to-host copy
+        B = int(bi.max().item()) + 1 if B is None else int(B)
         batch.x = _segment_mean_sub(batch.x, bi, B, mask)                         # centralize(..., edm=True): translation-invariant positions
         batch.h = {"categorical": batch.one_hot, "integer": batch.charges}
         ctx = getattr(batch, "props_context", None)

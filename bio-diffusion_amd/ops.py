@@ -321,6 +321,26 @@ class Graph:
             raise ValueError("edge_index must be sorted by its first row (source node), as get_fully_connected_edge_index produces it")
         self._col_order = None
 
+    @classmethod
+    def from_parts(cls, edge_index: torch.Tensor, num_nodes: int, rowptr: torch.Tensor, colperm: torch.Tensor, colptr: torch.Tensor) -> "Graph":
+        """Trusted constructor: the caller (the data loader's collation kernel, include/gcdm_data.h) vouches that ``edge_index`` [2, E] int64 is
+        sorted by row with every index in [0, num_nodes), and that rowptr / (colperm, colptr) are what ``Graph(edge_index, num_nodes)`` and
+        ``col_order()`` would compute.  Shapes and dtypes are checked on the host; no launch, no device-to-host copy."""
+        _shape(edge_index.dim() == 2 and edge_index.shape[0] == 2 and edge_index.dtype == torch.int64 and edge_index.is_contiguous(),
+               f"edge_index {tuple(edge_index.shape)} {edge_index.dtype} must be a contiguous int64 [2, E]")
+        N, E = int(num_nodes), int(edge_index.shape[1])
+        _shape(N >= 0, f"num_nodes = {num_nodes}")
+        for name, t, n, dt in (("rowptr", rowptr, N + 1, torch.int32), ("colperm", colperm, E, torch.int64), ("colptr", colptr, N + 1, torch.int32)):
+            _shape(t.dim() == 1 and t.shape[0] == n and t.dtype == dt and t.is_contiguous() and t.device == edge_index.device,
+                   f"{name} {tuple(t.shape)} {t.dtype} must be a contiguous {dt} [{n}] on {edge_index.device}")
+        _dev(edge_index)
+        g = cls.__new__(cls)
+        g.edge_index, g.row, g.col = edge_index, edge_index[0], edge_index[1]
+        g.N, g.E = N, E
+        g.rowptr = rowptr
+        g._col_order = (colperm, colptr)
+        return g
+
     def col_order(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(colperm, colptr): a stable argsort of col and the CSR pointers of col[colperm] -- the fixed order of every column sum of the fused
         message layer's backward.  Computed once per graph."""
@@ -346,6 +366,14 @@ def graph_of(edge_index: torch.Tensor, num_nodes: int) -> Graph:
     return g
 
 
+def register_graph(graph: Graph, edge_index: torch.Tensor) -> None:
+    """Makes ``graph_of(edge_index, graph.N)`` return ``graph`` (a Graph.from_parts of that very tensor) instead of building one."""
+    _shape(edge_index.dim() == 2 and edge_index.shape[0] == 2 and edge_index.shape[1] == graph.E and edge_index[0].data_ptr() == graph.row.data_ptr(),
+           "register_graph: the graph was not made from this edge_index")
+    key = (edge_index.data_ptr(), tuple(edge_index.shape), _native.tensor_version(edge_index), int(graph.N))
+    _GRAPH_CACHE["g"], _GRAPH_CACHE["key"], _GRAPH_CACHE["keep"] = graph, key, edge_index
+
+
 class _Gather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, graph, by_row):
@@ -355,6 +383,8 @@ class _Gather(torch.autograd.Function):
         out = torch.empty((graph.E, xs.shape[1]), dtype=torch.float32, device=xs.device)
         _chk(_lib().gcdm_op_gather(_p(xs), _p(idx), _p(out), graph.E, xs.shape[1], _st(xs)), "gcdm_op_gather")
         ctx.graph, ctx.by_row, ctx.shape = graph, by_row, x.shape
+        if not by_row and ctx.needs_input_grad[0]:
+            graph.col_order()          # the backward's fixed summation order, made here: once per graph, on the forward's stream
         return out.reshape(graph.E, *x.shape[1:])
 
     @staticmethod
@@ -364,9 +394,13 @@ class _Gather(torch.autograd.Function):
         if ctx.by_row:           # sorted index: a deterministic segment sum
             dx = torch.empty((ctx.graph.N, Cn), dtype=torch.float32, device=g.device)
             _chk(_lib().gcdm_op_segment_sum(_p(g), _p(ctx.graph.rowptr), _p(dx), ctx.graph.N, Cn, 0, _st(g)), "gcdm_op_segment_sum")
-        else:
-            dx = torch.zeros((ctx.graph.N, Cn), dtype=torch.float32, device=g.device)
-            _chk(_lib().gcdm_op_scatter_add(_p(g), _p(ctx.graph.col), _p(dx), ctx.graph.E, Cn, _st(g)), "gcdm_op_scatter_add")
+        else:                    # column index: the rows in the graph's stable column order, then the same segment sum -- no atomics, so the
+            # gradient has the same bits from run to run (the order is the one the fused message layer's backward sums in)
+            colperm, colptr = ctx.graph.col_order()
+            by_col = torch.empty_like(g)
+            _chk(_lib().gcdm_op_gather(_p(g), _p(colperm), _p(by_col), ctx.graph.E, Cn, _st(g)), "gcdm_op_gather")
+            dx = torch.empty((ctx.graph.N, Cn), dtype=torch.float32, device=g.device)
+            _chk(_lib().gcdm_op_segment_sum(_p(by_col), _p(colptr), _p(dx), ctx.graph.N, Cn, 0, _st(g)), "gcdm_op_segment_sum")
         return dx.reshape(ctx.shape), None, None
 
 
