@@ -54,8 +54,15 @@ def ensure_bond_arrays(dataset_info: Dict[str, Any]) -> Dict[str, Any]:
     return dataset_info
 
 
+def _fp32_ceil(v: float) -> float:
+    """The smallest fp32 value >= v.  The reference compares the fp32 distance, widened, with the float64 threshold; for an fp32 d,
+    d < v holds exactly when d < this value, so the kernel's fp32 comparison decides as the reference's does for any threshold."""
+    f = np.float32(v)
+    return float(f if float(f) >= v else np.nextafter(f, np.float32(np.inf)))
+
+
 def bond_tables(dataset_info: Dict[str, Any], limit_bonds_to_one: bool = False) -> "_native.GcdmBondTables":
-    """Packs `dataset_info["bonds1..3"]` (+ margins) and `allowed_bonds` into the ABI struct."""
+    """Packs `dataset_info["bonds1..3"]` (+ margins, rounded up to fp32) and `allowed_bonds` into the ABI struct."""
     ensure_bond_arrays(dataset_info)
     const = bond_constants()
     decoder = dataset_info["atom_decoder"]
@@ -70,7 +77,7 @@ def bond_tables(dataset_info: Dict[str, Any], limit_bonds_to_one: bool = False) 
         dst = getattr(tb, name)
         for a in range(T):
             for b in range(T):
-                dst[a * M + b] = float(arr[a, b] + margin)
+                dst[a * M + b] = _fp32_ceil(arr[a, b] + margin)
     for a, sym in enumerate(decoder):
         allowed = const["allowed_bonds"][sym]
         mask = 0

@@ -283,7 +283,9 @@ double gcdm_forward_flops_executed(const gcdm_handle* h);
 typedef struct GcdmBondTables {
     int32_t  num_types;                 /* T = len(dataset_info["atom_decoder"]) <= 16 */
     int32_t  limit_bonds_to_one;        /* get_bond_order_batch(limit_bonds_to_one=...) ; check_molecular_stability uses 0 */
-    /* thrK[a*16 + b] = bondsK[a][b] + marginK in pm (bond length 0 where the pair has no entry, exactly as get_bond_length_arrays) */
+    /* thrK[a*16 + b] = bondsK[a][b] + marginK in pm (bond length 0 where the pair has no entry, exactly as get_bond_length_arrays).  The
+     * reference compares the fp32 distance with the float64 sum: store the smallest fp32 >= that sum (round up, not to nearest), and the
+     * kernel's fp32 `d < thr` decides alike for every fp32 d.  Integer tables, the shipped ones, are stored as they are. */
     float    thr1[GCDM_STABILITY_MAX_TYPES * GCDM_STABILITY_MAX_TYPES];
     float    thr2[GCDM_STABILITY_MAX_TYPES * GCDM_STABILITY_MAX_TYPES];
     float    thr3[GCDM_STABILITY_MAX_TYPES * GCDM_STABILITY_MAX_TYPES];
@@ -293,16 +295,20 @@ typedef struct GcdmBondTables {
 /* For every molecule m (atoms mol_offsets[m] .. mol_offsets[m+1]-1) writes out[m] = {molecule_stable, nr_stable_atoms, n}.
  *   tables      host   (copied into the launch; nothing is retained)
  *   x           device fp32, atom i at x[i * x_row_stride .. +2]  (pass the sampler output xh with x_row_stride = 3+F)
- *   atom_types  device int32 [N] in [0, T)
+ *   atom_types  device int32 [N]; a type outside [0, T) reads no table entry: that atom has bond order 0 to and from every atom and
+ *               counts as unstable, the other atoms of the molecule fare as if it were absent
  *   mol_offsets device int32 [num_molecules + 1], ascending
  *   out         device int32 [num_molecules][3]
+ * Distances are 100 * sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) in fp32 with a correctly rounded root, the arithmetic of torch.cdist's
+ * direct path (n <= 25 in the reference), at every molecule size; a pair bonds at order k when the distance is strictly below thrK, later
+ * k overwriting earlier ones.  Molecules may be empty.  Bad arguments and num_molecules = 0 write nothing.
  * Handle-free; returns 0, -1 (bad argument) or -2 (HIP launch error). */
 int gcdm_check_stability(const GcdmBondTables* tables, const float* x, int64_t x_row_stride, const int32_t* atom_types,
                          const int32_t* mol_offsets, int32_t num_molecules, int32_t* out, void* stream);
 
 /* Bond orders of every atom pair (get_bond_order_batch, src/datamodules/components/edm/__init__.py:61-87; what make_mol_edm,
  * rdkit_functions.py:276-320, builds its molecules from): for molecule m an n x n uint8 matrix at orders[pair_offsets[m] ..], entry
- * (i, j) = 0 / 1 / 2 / 3, diagonal 0.  Same arguments as gcdm_check_stability; pair_offsets device int64 [num_molecules], orders device
+ * (i, j) = 0 / 1 / 2 / 3, diagonal 0, every element of the block written and nothing outside it.  Same arguments as gcdm_check_stability; pair_offsets device int64 [num_molecules], orders device
  * uint8 [sum n^2].  Feeds the SDF / molfile writer (write_sdf_file, src/models/components/__init__.py:372-378) without RDKit. */
 int gcdm_bond_orders(const GcdmBondTables* tables, const float* x, int64_t x_row_stride, const int32_t* atom_types,
                      const int32_t* mol_offsets, int32_t num_molecules, const int64_t* pair_offsets, uint8_t* orders, void* stream);

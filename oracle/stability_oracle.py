@@ -50,7 +50,7 @@ def bond_order_batch(atoms1: np.ndarray, atoms2: np.ndarray, distances: np.ndarr
 def pair_distances(positions: np.ndarray, direct: bool = False) -> np.ndarray:
     """`torch.cdist(x, x, p=2)` as the reference calls it (:104).  ATen evaluates sqrt(sum d^2) directly for n <= 25 and switches
     to the |x|^2 + |y|^2 - 2 x.y expansion above that (`use_mm_for_euclid_dist_if_necessary`); `direct=True` forces the former."""
-    x = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float32))
+    x = torch.from_numpy(np.array(positions, dtype=np.float32, order="C"))         # a copy: the caller's array may be read-only
     mode = "donot_use_mm_for_euclid_dist" if direct else "use_mm_for_euclid_dist_if_necessary"
     return torch.cdist(x, x, p=2.0, compute_mode=mode).numpy()
 
@@ -61,15 +61,25 @@ def allowed(tables: Dict[str, Any], symbol: str, nr_bonds: int) -> bool:
     return (pb == nr_bonds) if isinstance(pb, int) else (nr_bonds in pb)
 
 
-def check_molecular_stability(positions: np.ndarray, atom_types: np.ndarray, atom_decoder: Sequence[str], tables: Dict[str, Any],
-                              bonds: Sequence[np.ndarray], direct: bool = False) -> Tuple[bool, int, int]:
-    """edm/__init__.py:91-122 -> (molecule_stable, nr_stable_atoms, n)."""
+def bond_order_matrix(positions: np.ndarray, atom_types: np.ndarray, bonds: Sequence[np.ndarray], margins: Sequence[float],
+                      limit_bonds_to_one: bool = False, direct: bool = False) -> np.ndarray:
+    """:104-109 -- the [n, n] bond orders of one molecule from `torch.cdist`, diagonal 0."""
     n = len(positions)
     dist = pair_distances(positions, direct).reshape(-1)
     t = np.asarray(atom_types, np.int64)
     a1, a2 = np.meshgrid(t, t, indexing="xy")
-    order = bond_order_batch(a1.reshape(-1), a2.reshape(-1), dist, bonds, tables["margins"]).reshape(n, n)
+    order = bond_order_batch(a1.reshape(-1), a2.reshape(-1), dist, bonds, margins, limit_bonds_to_one).reshape(n, n)
     np.fill_diagonal(order, 0)
+    return order
+
+
+def check_molecular_stability(positions: np.ndarray, atom_types: np.ndarray, atom_decoder: Sequence[str], tables: Dict[str, Any],
+                              bonds: Sequence[np.ndarray], direct: bool = False, limit_bonds_to_one: bool = False) -> Tuple[bool, int, int]:
+    """edm/__init__.py:91-122 -> (molecule_stable, nr_stable_atoms, n).  The reference never limits the orders here; the flag exists because
+    the C entry point takes it."""
+    n = len(positions)
+    t = np.asarray(atom_types, np.int64)
+    order = bond_order_matrix(positions, t, bonds, tables["margins"], limit_bonds_to_one, direct)
     nr_bonds = order.sum(axis=1)
     stable = sum(int(allowed(tables, atom_decoder[int(ti)], int(nb))) for ti, nb in zip(t, nr_bonds))
     return stable == n, stable, n
