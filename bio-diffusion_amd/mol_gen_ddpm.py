@@ -95,6 +95,57 @@ def load_lightning_state_dict(path: str) -> Dict[str, torch.Tensor]:
     return ckpt["state_dict"] if "state_dict" in ckpt else ckpt
 
 
+CHUNKED_EVAL_BASE_SEED = 1234      # evaluate_conditional's chunked modes without `seed`: batch i runs with 1234 + i, as sample_and_analyze's batches do
+_CHUNKED_EVAL_REFUSED = ("node_mask", "fix_noise", "lanes", "noise_fn", "step_callback", "return_frames")
+
+
+def _chunked_eval_mode(packed_batches: Optional[int], concurrent_batches: int) -> Tuple[str, int]:
+    """("sequential" | "concurrent" | "packed", K) of evaluate_conditional's two arguments; sample_and_analyze's rules and wording."""
+    if packed_batches is not None:
+        if int(concurrent_batches) > 1:
+            raise ValueError("packed_batches and concurrent_batches > 1 exclude each other: batches are either packed into one plan or run on lane handles")
+        if int(packed_batches) < 1:
+            raise ValueError("packed_batches must be >= 1")
+        return "packed", int(packed_batches)
+    if int(concurrent_batches) > 1:
+        return "concurrent", int(concurrent_batches)
+    return "sequential", 1
+
+
+def _refuse_for_chunked_eval(mode: str, self_conditioned: bool, sample_kw: Dict[str, Any]) -> None:
+    """What mol_gen_sample_packed / mol_gen_sample_concurrent cannot honour, refused by name before anything is drawn or launched."""
+    arg = "packed_batches" if mode == "packed" else "concurrent_batches"
+    if mode == "packed" and self_conditioned:
+        raise NotImplementedError("evaluate_conditional: packed_batches does not serve a self-conditioned model (mol_gen_sample_packed refuses it); "
+                                  "leave packed_batches out")
+    for name in sample_kw:
+        if name in _CHUNKED_EVAL_REFUSED:
+            raise ValueError(f"evaluate_conditional: {name} cannot be honoured with {arg} (the batches of a chunk are plain samples on the device's own "
+                             f"noise); leave {arg} out to pass {name}")
+        if name != "num_timesteps":
+            raise ValueError(f"evaluate_conditional: {name} is not passed on with {arg}: only num_timesteps is")
+
+
+def conditional_eval_plan(iterations: int, K: int, seed: Optional[int], mode: str) -> Tuple[List[List[int]], List[Optional[int]]]:
+    """The batches of one evaluate_conditional call: (chunks, seeds).  ``chunks`` lists the batch numbers 0 .. iterations of each sampling call, in
+    order (``mode`` "sequential": one batch per call whatever K; "concurrent" / "packed": K per call, the last one shorter if need be);
+    ``seeds[i]`` is the seed of batch i: ``seed + i``, with 1234 for a ``seed`` of None in the two chunked modes, and None -- the sampler's own
+    default, the same for every batch -- in the sequential one."""
+    if mode not in ("sequential", "concurrent", "packed"):
+        raise ValueError(f"unknown mode {mode!r}")
+    n = int(iterations) + 1
+    if n < 1:
+        raise ValueError("iterations must be >= 0")
+    K = 1 if mode == "sequential" else int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    if seed is None:
+        seeds = [None] * n if mode == "sequential" else [CHUNKED_EVAL_BASE_SEED + i for i in range(n)]
+    else:
+        seeds = [int(seed) + i for i in range(n)]
+    return [list(range(i0, min(i0 + K, n))) for i0 in range(0, n, K)], seeds
+
+
 class _MoleculeGenerationDDPM(nn.Module):
     _DATASETS: Dict[str, str] = {}
 
@@ -443,7 +494,8 @@ class _MoleculeGenerationDDPM(nn.Module):
                  optim_property: Optional[str] = None, iteration_index: Optional[int] = None, return_frames: int = 1, id_from: int = 0,
                  chain_viz_batch_element_idx: int = 0, name: str = os.sep + "chain", norm_with_original_timesteps: bool = False,
                  verbose: bool = True, **kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-        """qm9_mol_gen_ddpm.py:636-743: property-guided optimisation of existing samples.  ``return_frames > 1`` (:674-731): the chain of molecule
+        """qm9_mol_gen_ddpm.py:636-743: property-guided optimisation of existing samples (``samples``: the reference's list of (x, one_hot) pairs, or
+        the flat pair (x [N,3], one_hot [N,F]) this method returns -- see ``mol_gen_optimize``).  ``return_frames > 1`` (:674-731): the chain of molecule
         ``chain_viz_batch_element_idx`` -- frames in generation order, the last one repeated 10 times -- goes out as one XYZ file per frame under
         ``<sampling_output_dir>/<optim_property>/<time stamp>/iteration_<i>/chain`` (the reference then renders them with matplotlib / imageio:
         visualisation, not built), and the returned x / one_hot are frame 0 = the optimised molecules."""
@@ -546,7 +598,8 @@ class _MoleculeGenerationDDPM(nn.Module):
     @torch.inference_mode()
     def evaluate_conditional(self, classifier: Any, property: str, mean: float, mad: float, iterations: int, batch_size: int,
                              props_distr: Any = None, unknown_labels: bool = False, save_molecules: bool = False,
-                             sampling_output_dir: Optional[str] = None, **sample_kw) -> Tuple[float, List[Dict[str, Any]]]:
+                             sampling_output_dir: Optional[str] = None, packed_batches: Optional[int] = None, concurrent_batches: int = 1,
+                             seed: Optional[int] = None, **sample_kw) -> Tuple[float, List[Dict[str, Any]]]:
         """The conditional-evaluation driver, src/mol_gen_eval_conditional_qm9.py:101-156 and :303-315 on the device: per batch draw the sizes,
         draw the (normalised) context from ``props_distr.sample_batch``, ``sample``, de-normalise the label with ``props_distr.normalizer``
         (``unknown_labels``: the label is the property's mean), classify the samples (classifier.EGNN.predict: one launch, no copy of the
@@ -554,7 +607,22 @@ class _MoleculeGenerationDDPM(nn.Module):
         ``i <= iterations``, i.e. ``iterations + 1`` batches; so does this.  ``props_distr`` is duck-typed (``sample_batch``, ``properties``,
         ``normalizer``) and defaults to ``self.props_distr``.  ``save_molecules`` writes each batch's XYZ files under
         ``<sampling_output_dir>/run<i>/``.  Returns the MAE and one record per batch (loss, num_nodes, label, pred and the samples x / one_hot,
-        all left on the device)."""
+        all left on the device).
+
+        Seeds.  The default call samples EVERY batch with the sampler's default seed (1234): device noise is a pure function of (seed, node index
+        within the batch, draw number), so all ``iterations + 1`` batches share one noise tape and differ only through their sizes and contexts --
+        the reference's global RNG advances between batches instead.  That default is kept as it is; pass ``seed`` to give batch ``i`` the seed
+        ``seed + i`` and with it noise of its own.
+
+        ``packed_batches = K`` / ``concurrent_batches = K > 1`` (they exclude each other, as in ``sample_and_analyze``): the sizes and contexts of
+        all batches are drawn first, in the sequential order (sizes of batch 0, context of batch 0, sizes of batch 1, ...), then the batches run in
+        chunks of K through ``mol_gen_sample_packed`` / ``mol_gen_sample_concurrent`` with seed ``base + i`` for batch ``i`` (``base``: ``seed``,
+        or 1234), a chunk is classified in one launch and its per-batch losses reach the host in one copy.  Records, files and -- with the same
+        ``seed`` and ``lanes=1`` on the sequential side -- samples are those of the sequential call.  These modes take ``num_timesteps`` in
+        ``sample_kw`` and nothing else, and ``packed_batches`` no self-conditioned model: refused before any work."""
+        mode, K = _chunked_eval_mode(packed_batches, concurrent_batches)
+        if mode != "sequential":
+            _refuse_for_chunked_eval(mode, bool(getattr(self.ddpm.dynamics_network, "self_condition", False)), sample_kw)
         if not self.condition_on_context:
             raise Exception("Conditional evaluation requires a conditional model (module_cfg.conditioning).")
         props_distr = self.props_distr if props_distr is None else props_distr
@@ -564,11 +632,16 @@ class _MoleculeGenerationDDPM(nn.Module):
         if prop_key != property:
             raise ValueError(f"props_distr conditions on {prop_key!r}, the classifier is evaluated on {property!r}")
         norm = props_distr.normalizer[prop_key]
+        if mode != "sequential":
+            return self._evaluate_conditional_chunked(classifier, mean, mad, norm, props_distr, unknown_labels, int(iterations), batch_size, mode, K,
+                                                      seed, sample_kw.get("num_timesteps"), save_molecules, sampling_output_dir)
         total, count, records = 0.0, 0, []
         for i in range(int(iterations) + 1):
             num_nodes = self.ddpm.num_nodes_distribution.sample(batch_size)
             assert int(num_nodes.max()) <= self.dataset_info.get("max_n_nodes", int(num_nodes.max()))
             context = props_distr.sample_batch(num_nodes).to(self.device)
+            if seed is not None:
+                sample_kw["seed"] = int(seed) + i                                # (seed given: batch i draws its own noise)
             x, one_hot, charges, batch_index = self.sample(num_samples=batch_size, num_nodes=num_nodes, context=context, **sample_kw)
             if save_molecules:
                 out_dir = os.path.join(str(sampling_output_dir) if sampling_output_dir is not None else "sampling_output", f"run{i}")
@@ -585,6 +658,119 @@ class _MoleculeGenerationDDPM(nn.Module):
             count += batch_size
             records.append(dict(loss=loss, num_nodes=num_nodes, label=label, pred=pred, x=x, one_hot=one_hot))
         return total / count, records
+
+    def _evaluate_conditional_chunked(self, classifier, mean, mad, norm, props_distr, unknown_labels, iterations, batch_size, mode, K, seed,
+                                      num_timesteps, save_molecules, sampling_output_dir):
+        """evaluate_conditional with K batches per sampling call: the statements of the sequential loop, per chunk where they can be."""
+        chunks, seeds = conditional_eval_plan(iterations, K, seed, mode)
+        plan = []
+        for i in range(iterations + 1):                              # draw everything first: the same random streams as the sequential driver
+            num_nodes = self.ddpm.num_nodes_distribution.sample(batch_size)
+            assert int(num_nodes.max()) <= self.dataset_info.get("max_n_nodes", int(num_nodes.max()))
+            plan.append((num_nodes, props_distr.sample_batch(num_nodes).to(self.device)))
+        sampler = self.ddpm.mol_gen_sample_packed if mode == "packed" else self.ddpm.mol_gen_sample_concurrent
+        total, count, records = 0.0, 0, []
+        for chunk in chunks:
+            outs = sampler([plan[i][0] for i in chunk], self.device, num_timesteps=num_timesteps, contexts=[plan[i][1] for i in chunk],
+                           seeds=[seeds[i] for i in chunk])
+            xh = torch.cat([o[0] for o in outs], dim=0)
+            one_hot_all = xh[:, self.num_x_dims:-1] if self.include_charges else xh[:, self.num_x_dims:]
+            pred_all = classifier.predict(xh[:, : self.num_x_dims], one_hot_all, num_nodes=torch.cat([plan[i][0] for i in chunk]))   # one launch
+            losses, parts = [], []
+            for j, (i, (xh_b, batch_index, _)) in enumerate(zip(chunk, outs)):
+                num_nodes, context = plan[i]
+                x = xh_b[:, : self.num_x_dims]
+                one_hot = xh_b[:, self.num_x_dims:-1] if self.include_charges else xh_b[:, self.num_x_dims:]
+                charges = xh_b[:, -1:] if self.include_charges else torch.zeros(0, device=self.device)
+                if save_molecules:
+                    out_dir = os.path.join(str(sampling_output_dir) if sampling_output_dir is not None else "sampling_output", f"run{i}")
+                    save_xyz_file(path=out_dir + "/", positions=x, one_hot=one_hot, charges=charges, dataset_info=self.dataset_info,
+                                  id_from=i * batch_size, name="conditional", batch_index=batch_index)
+                label = context.reshape(batch_size, -1)[:, 0].to(torch.float32)
+                if unknown_labels:
+                    label = torch.full_like(label, float(norm["mean"]))
+                else:
+                    label = label * float(norm["mad"]) + float(norm["mean"])
+                pred = pred_all[j * batch_size:(j + 1) * batch_size]
+                losses.append((mad * pred + mean - label).abs().mean())          # the sequential statement on the same values: the same bits
+                parts.append(dict(num_nodes=num_nodes, label=label, pred=pred, x=x, one_hot=one_hot))
+            for loss, part in zip(torch.stack(losses).tolist(), parts):          # one copy per chunk reaches the host
+                total += loss * batch_size
+                count += batch_size
+                records.append(dict(loss=loss, **part))
+        return total / count, records
+
+    @torch.inference_mode()
+    def evaluate_optimization(self, classifier: Any, property: str, mean: float, mad: float, samples: Any, num_nodes: torch.Tensor,
+                              num_iterations: int, num_timesteps: int, context: Optional[torch.Tensor] = None, props_distr: Any = None,
+                              unknown_labels: bool = False, score_initial_samples: bool = True, seed: int = 1234, save_molecules: bool = False,
+                              sampling_output_dir: Optional[str] = None) -> List[Dict[str, Any]]:
+        """The optimisation-evaluation driver, src/mol_gen_eval_optimization_qm9.py:133-241 and :433-450 on the device: ``num_iterations`` times
+        ``optimize`` the samples for ``num_timesteps`` steps (``norm_with_original_timesteps=False``, as the reference insists), count the stable
+        molecules and atoms (``check_molecular_stability_batch``) and score the property classifier against the requested, de-normalised property.
+
+        ``samples``: the flat pair ``(x [N,3], one_hot [N,F])``, rows as ``num_nodes`` [B] lays them out, or the reference's list of B
+        ``(x, one_hot)`` pairs (concatenated once, up front).  ``context`` [B, 1] (normalised) is kept for all iterations, as in the reference;
+        without it, it is drawn once from ``props_distr`` (default ``self.props_distr``).  The label is ``context * mad + mean`` with the mean / mad
+        of ``props_distr.normalizer`` when a ``props_distr`` is there, else with the classifier's ``mean`` / ``mad`` (the reference builds both from
+        the same statistics); ``unknown_labels``: the label is that mean.  Iteration ``it`` runs with ``seed + it``: with one seed for all of them
+        every iteration would add the very same noise tape to its input.
+
+        Between iterations the samples stay flat on the device -- no per-molecule masks, no list -- and per iteration the three stability integers
+        per molecule and one scalar reach the host.  ``save_molecules`` writes iteration ``it`` to ``<sampling_output_dir>/run<it + 2>/`` (the
+        reference's numbering: run 1 is the scoring of the initial samples, which writes nothing).
+
+        Returns a list of records ``dict(iteration, mae, mol_stable, atm_stable, x, one_hot)``: first the initial samples (``iteration`` None) when
+        ``score_initial_samples``, then iterations 0 .. num_iterations - 1; ``x`` / ``one_hot`` stay on the device."""
+        if not self.condition_on_context:
+            raise Exception("Optimization requires a context conditional to optimize (e.g., `alpha`).")
+        if self.include_charges:
+            raise NotImplementedError("mol_gen_optimize builds z without the charge column (reference :1457): include_charges must be False")
+        if int(num_iterations) < 1:
+            raise ValueError(f"num_iterations must be >= 1, got {num_iterations}")
+        num_nodes = torch.as_tensor(num_nodes).cpu()
+        if len(samples) == 2 and all(torch.is_tensor(s) for s in samples):
+            x, one_hot = samples
+        else:
+            if len(samples) != len(num_nodes):
+                raise ValueError(f"{len(samples)} (x, one_hot) pairs for {len(num_nodes)} molecules in num_nodes")
+            x, one_hot = torch.cat([s[0] for s in samples], dim=0), torch.cat([s[1] for s in samples], dim=0)
+        if x.shape[0] != int(num_nodes.sum()) or one_hot.shape[0] != x.shape[0]:
+            raise ValueError(f"samples have {x.shape[0]} / {one_hot.shape[0]} rows (x / one_hot), num_nodes sums to {int(num_nodes.sum())}")
+        props_distr = self.props_distr if props_distr is None else props_distr
+        if props_distr is not None and props_distr.properties[0] != property:
+            raise ValueError(f"props_distr conditions on {props_distr.properties[0]!r}, the classifier is evaluated on {property!r}")
+        if context is None:
+            if props_distr is None:
+                raise ValueError("evaluate_optimization needs context or props_distr (none attached)")
+            context = props_distr.sample_batch(num_nodes)
+        norm = props_distr.normalizer[property] if props_distr is not None else {"mean": mean, "mad": mad}
+        B = len(num_nodes)
+        context = context.to(self.device)
+        label = context.reshape(B, -1)[:, 0].to(torch.float32)
+        if unknown_labels:
+            label = torch.full_like(label, float(norm["mean"]))
+        else:
+            label = label * float(norm["mad"]) + float(norm["mean"])
+        x, one_hot = x.to(self.device, torch.float32), one_hot.to(self.device, torch.float32)
+
+        def record(iteration, x, one_hot):
+            st = check_molecular_stability_batch(x, one_hot.argmax(-1), num_nodes, self.dataset_info).cpu().to(torch.int64)   # 3 integers per molecule
+            pred = classifier.predict(x, one_hot, num_nodes=num_nodes)
+            mae = (mad * pred + mean - label).abs().mean().item()                # one scalar
+            return dict(iteration=iteration, mae=mae, mol_stable=float(st[:, 0].sum()) / float(B), atm_stable=float(st[:, 1].sum()) / float(st[:, 2].sum()),
+                        x=x, one_hot=one_hot)
+
+        records = [record(None, x, one_hot)] if score_initial_samples else []
+        for it in range(int(num_iterations)):
+            x, one_hot, charges, batch_index = self.optimize((x, one_hot), num_timesteps=num_timesteps, num_nodes=num_nodes, context=context,
+                                                             norm_with_original_timesteps=False, seed=int(seed) + it)
+            if save_molecules:
+                out_dir = os.path.join(str(sampling_output_dir) if sampling_output_dir is not None else "sampling_output", f"run{it + 2}")
+                save_xyz_file(path=out_dir + "/", positions=x, one_hot=one_hot, charges=charges, dataset_info=self.dataset_info,
+                              id_from=0, name="conditional", batch_index=batch_index)
+            records.append(record(it, x, one_hot))
+        return records
 
     def analyze_samples(self, stability: torch.Tensor, atom_type_counts: torch.Tensor) -> Dict[str, Any]:
         """qm9_mol_gen_ddpm.py:846-885 on the device results: `stability` int [M, 3] rows (stable, nr_stable_atoms, n)."""

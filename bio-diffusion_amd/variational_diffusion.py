@@ -965,7 +965,8 @@ class EquivariantVariationalDiffusion(nn.Module):
                          noise_fn: Optional[Callable[[int], torch.Tensor]] = None, seed: int = 1234
                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Optimise existing samples with the generative model (variational_diffusion.py:1416-1546): the samples
-        ``[(x [n,3], one_hot [n,F]), ...]`` are normalised and taken as z at t = num_timesteps / T_norm, denoised for ``num_timesteps``
+        ``[(x [n,3], one_hot [n,F]), ...]`` -- or one flat pair ``(x [N,3], one_hot [N,F])`` of all molecules, rows as ``num_nodes`` lays them
+        out -- are normalised and taken as z at t = num_timesteps / T_norm, denoised for ``num_timesteps``
         steps and decoded.  As in the reference z carries no charge column (``"integer": torch.tensor([])``, :1457), so the model must
         have ``include_charges=False`` (the property-conditional QM9 models).  ``noise_fn(k)``: k = 0 is the first step's draw.
         ``return_frames > 1``: [frames, N, 3 + F] -- frame (s * return_frames) // T after the step to s, frame 0 the decoded sample (:1490-1497,
@@ -976,9 +977,18 @@ class EquivariantVariationalDiffusion(nn.Module):
             raise NotImplementedError("mol_gen_optimize: generate_x_only raises in the reference too (variational_diffusion.py:716 via :1454: `h.float()` on a dict)")
         if self.include_charges:
             raise NotImplementedError("mol_gen_optimize builds z without the charge column (reference :1457): include_charges must be False")
-        if len(samples) != len(num_nodes):
-            raise ValueError("one (x, h) pair per molecule")
-        xh = torch.cat([torch.cat((x.to(torch.float32), h.to(torch.float32)), dim=-1) for x, h in samples], dim=0)
-        return self.mol_gen_sample(num_samples=len(samples), num_nodes=num_nodes, device=device, return_frames=return_frames, num_timesteps=num_timesteps,
+        if len(samples) == 2 and all(torch.is_tensor(s) for s in samples):
+            # the flat form, what sample() / optimize() return: (x [N,3], one_hot [N,F]) of all molecules, the atoms of a molecule contiguous
+            x, h = samples
+            if x.shape[0] != h.shape[0] or x.shape[0] != int(torch.as_tensor(num_nodes).sum()):
+                raise ValueError(f"flat samples have {x.shape[0]} / {h.shape[0]} rows, num_nodes sums to {int(torch.as_tensor(num_nodes).sum())}")
+            xh = torch.cat((x.to(torch.float32), h.to(torch.float32)), dim=-1)
+            n_samples = len(num_nodes)
+        else:
+            if len(samples) != len(num_nodes):
+                raise ValueError("one (x, h) pair per molecule")
+            xh = torch.cat([torch.cat((x.to(torch.float32), h.to(torch.float32)), dim=-1) for x, h in samples], dim=0)
+            n_samples = len(samples)
+        return self.mol_gen_sample(num_samples=n_samples, num_nodes=num_nodes, device=device, return_frames=return_frames, num_timesteps=num_timesteps,
                                    node_mask=node_mask, context=context, norm_with_original_timesteps=norm_with_original_timesteps,
                                    noise_fn=noise_fn, seed=seed, _init_xh=xh)
