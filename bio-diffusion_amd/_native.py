@@ -27,6 +27,7 @@ OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(
                os.path.join(_HERE, "csrc", "gcdm_ops.objective.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_objective.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.bucket.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_grad_bucket.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.data.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_data.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.geom.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_geom.h"),
                os.path.join(os.path.dirname(_HERE), "include", "gcdm_matrix_mode.h")]
 ABI_VERSION = 2
 
@@ -232,6 +233,17 @@ DATA_SIGNATURES = {
 DATA_RESTYPES = {"gcdm_data_workspace_bytes": C.c_int64}
 DATA_MAX_TYPES, DATA_MAX_PROPS, DATA_MAX_SIZES, DATA_MAX_BINS = 16, 32, 2048, 65536          # GCDM_DATA_MAX_*
 DATA_FLAG_ABSENT_SIZE, DATA_FLAG_ACCOUNT = 1, 2                                               # GCDM_DATA_FLAG_*
+# the GEOM-Drugs conformer file on the device: ingestion chunk by chunk, the ragged reorder (include/gcdm_geom.h), exported from the same library
+GEOM_SIGNATURES = {
+    "gcdm_geom_workspace_bytes": [I32, I64],
+    "gcdm_geom_ingest": [P, I64, I32, P, P, P, P, I64, I64, P, P, P],
+    "gcdm_geom_finish": [P, P, I64, P, P, P],
+    "gcdm_geom_gather": [P, P, P, I64, I64, P, P, I64, I64, P, P, P, P],
+}
+GEOM_RESTYPES = {"gcdm_geom_workspace_bytes": C.c_int64}
+GEOM_TILE, GEOM_STATE_WORDS, GEOM_MAX_ROWS = 1024, 4, 2147483647                              # GCDM_GEOM_*
+GEOM_FLAG_BAD_ROW, GEOM_FLAG_CAPACITY, GEOM_FLAG_ACCOUNT = 1, 2, 4                            # GCDM_GEOM_FLAG_*
+GEOM_WS_BYTES, GEOM_WS_LAUNCHES, GEOM_WS_TILE = 0, 1, 2                                       # GCDM_GEOM_WS_*
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -247,7 +259,7 @@ def load_ops() -> C.CDLL:
         fn = getattr(lib, name)
         fn.argtypes = sig
         fn.restype = {**MP_TRAIN_RESTYPES, **MP_TILE_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
-    for table, restypes in ((MATRIX_MODE_SIGNATURES, MATRIX_MODE_RESTYPES), (DATA_SIGNATURES, DATA_RESTYPES)):
+    for table, restypes in ((MATRIX_MODE_SIGNATURES, MATRIX_MODE_RESTYPES), (DATA_SIGNATURES, DATA_RESTYPES), (GEOM_SIGNATURES, GEOM_RESTYPES)):
         for name, sig in table.items():
             fn = getattr(lib, name)
             fn.argtypes = sig

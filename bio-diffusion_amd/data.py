@@ -7,13 +7,20 @@ What it replaces in the reference (BioinfoMachineLearning/bio-diffusion): ``Proc
 (src/models/__init__.py:63-76, 311-415).  A batch also carries what the network would otherwise rebuild from it with device-to-host copies:
 the fully connected graph with its CSR (``fc_graph``), ``all_present`` and ``num_graphs``.
 
-Out of scope: downloading or pre-processing raw QM9 / GEOM, ``remove_h``, GEOM's same-size ``CustomBatchSampler`` (``sequential``),
-overlapping the collation with the previous step on a side stream, Lightning.  There is no CPU path: the data set lives on an MI355X.
+GEOM-Drugs comes from the reference's own conformer file (``GEOM_drugs_30.npy`` + ``GEOM_permutation.npy``): ``MoleculeDataset.geom_splits``
+uploads it in chunks and segments, strips (``remove_h``), filters, splits and size-sorts it in HBM (include/gcdm_geom.h), replacing
+``load_split_data`` + ``GeomDrugsDataset`` (src/datamodules/components/edm/build_geom_dataset.py:89-212); ``loader(sequential=True)`` gives the
+same-size batches of its ``CustomBatchSampler`` (:215-242).
+
+Out of scope: downloading or pre-processing raw QM9 / GEOM (``extract_conformers`` from the msgpack), ``remove_h`` for QM9, sequential batches
+under data-parallel ranks, overlapping the upload with the ingestion or the collation with the previous step on a side stream, Lightning.
+There is no CPU path: the data set lives on an MI355X.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from typing import Any, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
@@ -71,6 +78,53 @@ def batch_accounting(sizes: np.ndarray, pad_to: int):
     return N, int((sizes * sizes).sum()), bool(pad_to == 0 or (sizes == pad_to).all())
 
 
+# the atomic numbers of dataset_info("geom")["atom_decoder"], in its order: the one-hot columns of a GEOM-Drugs batch
+GEOM_ATOMIC_NUMBERS = (1, 5, 6, 7, 8, 9, 13, 14, 15, 16, 17, 33, 35, 53, 80, 83)
+GEOM_SPLITS = ("train", "valid", "test")
+
+
+def geom_split_orders(sizes: np.ndarray, permutation: np.ndarray, val_proportion: float = 0.1, test_proportion: float = 0.1,
+                      filter_size: Optional[int] = None) -> Dict[str, Any]:
+    """``{split: (order, split_indices)}`` from the atom counts of the file's molecules, as ``load_split_data`` + ``GeomDrugsDataset`` make them
+    (build_geom_dataset.py:104-128, 157-161): molecules of more than ``filter_size`` atoms leave, ``permutation`` indexes what is left, the cuts
+    are ``[valid | test | train]``, and each split is sorted by ``np.argsort`` of its sizes -- the reference's very call, whose order among equal
+    sizes is numpy's.  ``order`` names molecules of the file, ``split_indices`` the positions in the sorted split at which the size changes."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    kept = np.arange(len(sizes)) if filter_size is None else np.flatnonzero(sizes <= filter_size)
+    if filter_size is not None and len(kept) == 0:
+        raise ValueError("No molecules left after filter.")
+    perm = np.asarray(permutation).reshape(-1).astype(np.int64)
+    if len(perm) and (int(perm.min()) < -len(kept) or int(perm.max()) >= len(kept)):
+        raise IndexError(f"the permutation names molecule {int(perm.max())} (or {int(perm.min())}) of {len(kept)}")
+    picked = kept[perm]
+    val_index = int(len(picked) * val_proportion)
+    test_index = val_index + int(len(picked) * test_proportion)
+    out = {}
+    for name, ids in (("valid", picked[:val_index]), ("test", picked[val_index:test_index]), ("train", picked[test_index:])):
+        lengths = sizes[ids]
+        out[name] = (ids[np.argsort(lengths)], np.unique(np.sort(lengths), return_index=True)[1][1:].astype(np.int64))
+    return out
+
+
+def sequential_batches(n: int, batch_size: int, drop_last: bool, split_indices: np.ndarray):
+    """(first, count) of ``CustomBatchSampler``'s batches over ``range(n)`` (build_geom_dataset.py:215-242): consecutive indices, a batch closed
+    at ``batch_size`` or where ``idx + 1`` is in ``split_indices``; what is left open at the end is dropped by ``drop_last`` only."""
+    cuts = np.unique(np.asarray(split_indices, dtype=np.int64).reshape(-1))
+    cuts = cuts[(cuts >= 1) & (cuts <= n)]
+    edges = np.concatenate(([0], cuts, [n])).astype(np.int64)
+    firsts, counts = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
+    for a, b in zip(edges[:-1], edges[1:]):
+        if b > a:
+            first = np.arange(a, b, batch_size, dtype=np.int64)
+            firsts.append(first)
+            counts.append(np.minimum(batch_size, b - first))
+    firsts, counts = np.concatenate(firsts), np.concatenate(counts)
+    open_end = len(counts) > 0 and counts[-1] < batch_size and not (len(cuts) and cuts[-1] == n)
+    if drop_last and open_end:
+        firsts, counts = firsts[:-1], counts[:-1]
+    return firsts, counts
+
+
 class MoleculeDataset:
     """The reference's processed dictionary (``num_atoms [M]``, ``charges [M, A_max]``, ``positions [M, A_max, 3]``, optional ``index``, 1-D
     property arrays, ``<key>_thermo`` companions) after ProcessedDataset's filters, uploaded once in a ragged layout; the sizes stay mirrored on
@@ -120,7 +174,8 @@ class MoleculeDataset:
         if len(props) > _native.DATA_MAX_PROPS or len(included_species) > _native.DATA_MAX_TYPES:
             raise ValueError(f"at most {_native.DATA_MAX_PROPS} properties and {_native.DATA_MAX_TYPES} species")
         self.M, self.max_atoms = M, int(max_atoms)
-        self.num_pts = M if num_pts is None or num_pts < 0 else min(int(num_pts), M)
+        self.sorted_by_size, self.split_indices = False, None          # geom_splits sets them
+        self.num_pts =M if num_pts is None or num_pts < 0 else min(int(num_pts), M)
         self.included_species = included_species
         self.num_species, self.max_charge = len(included_species), (int(included_species.max()) if len(included_species) else 0)
         self.parameters = {"num_species": self.num_species, "max_charge": self.max_charge}
@@ -175,6 +230,91 @@ class MoleculeDataset:
                           max_atoms=int(n.max()) if len(confs) else 0)
         return self
 
+    @classmethod
+    def geom_splits(cls, file_or_array, device, permutation=None, val_proportion: float = 0.1, test_proportion: float = 0.1,
+                    filter_size: Optional[int] = None, remove_h: bool = False, included_species=None,
+                    chunk_rows: int = 1 << 22) -> Dict[str, "MoleculeDataset"]:
+        """``{"train", "valid", "test"}`` from the reference's conformer file: a path to ``GEOM_drugs_30.npy`` (memory-mapped, never read whole)
+        or the float64 array ``[A, 5]`` itself (molecule id, atomic number, x, y, z).  ``permutation=None`` reads ``GEOM_permutation.npy`` next
+        to the file, as ``load_split_data`` does.  The rows go up ``chunk_rows`` at a time through one pinned buffer and are segmented in HBM,
+        without hydrogens if ``remove_h`` (what ``extract_conformers --remove_h`` leaves); (M, A) and then the M sizes come back, the orders are
+        ``geom_split_orders`` of them, and each split is one ragged gather.  A split is sorted by size (``sorted_by_size``, ``split_indices``),
+        its ``index`` is the position in it, and ``included_species`` defaults to GEOM's atomic numbers (without 1 under ``remove_h``)."""
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("MoleculeDataset.geom_splits segments the conformer file on an MI355X: device must be a HIP ('cuda') device; there is "
+                               "no CPU fallback")
+        if isinstance(file_or_array, (str, os.PathLike)):
+            path = os.fspath(file_or_array)
+            rows = np.load(path, mmap_mode="r")
+            if permutation is None:
+                permutation = np.load(os.path.join(os.path.dirname(os.path.abspath(path)), "GEOM_permutation.npy"))
+        else:
+            rows = file_or_array if isinstance(file_or_array, np.ndarray) else np.asarray(file_or_array)
+            if permutation is None:
+                raise ValueError("an array has no GEOM_permutation.npy next to it: pass permutation")
+        if rows.ndim != 2 or rows.shape[1] != 5 or rows.dtype != np.float64:
+            raise ValueError(f"the conformer array must be float64 [A, 5] (molecule id, atomic number, x, y, z), got {rows.dtype} {rows.shape}")
+        R = int(rows.shape[0])
+        chunk_rows = max(1, min(int(chunk_rows), max(R, 1), _native.GEOM_MAX_ROWS))
+        if included_species is None:
+            included_species = [s for s in GEOM_ATOMIC_NUMBERS if not (remove_h and s == 1)]
+        included_species = torch.as_tensor(included_species).reshape(-1).to(torch.int32)
+        lib, stream = _lib(), _stream(dev)
+        # ingestion: every row could be a molecule of its own, so the capacities are the row count
+        z_all, pos_all = torch.empty(R, dtype=torch.int32, device=dev), torch.empty((R, 3), dtype=torch.float32, device=dev)
+        ptr_all = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        state, MA = torch.zeros(_native.GEOM_STATE_WORDS, dtype=torch.int64, device=dev), torch.zeros(2, dtype=torch.int64, device=dev)
+        flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(lib.gcdm_geom_workspace_bytes(_native.GEOM_WS_BYTES, chunk_rows)), dtype=torch.uint8, device=dev)
+        staging = torch.empty((chunk_rows, 5), dtype=torch.float64).pin_memory()
+        chunk = torch.empty((chunk_rows, 5), dtype=torch.float64, device=dev)
+        staged = torch.cuda.Event()
+        for r0 in range(0, R, chunk_rows):
+            r = min(chunk_rows, R - r0)
+            np.copyto(staging.numpy()[:r], rows[r0:r0 + r])
+            chunk[:r].copy_(staging[:r], non_blocking=True)
+            staged.record(torch.cuda.current_stream(dev))
+            _chk(lib.gcdm_geom_ingest(_ptr(chunk), r, int(bool(remove_h)), _ptr(state), _ptr(z_all), _ptr(pos_all), _ptr(ptr_all), R, R, _ptr(ws),
+                                      _ptr(flags), stream), "gcdm_geom_ingest")
+            staged.synchronize()                   # the pinned buffer is free for the next chunk; the kernels run on
+        _chk(lib.gcdm_geom_finish(_ptr(state), _ptr(ptr_all), R, _ptr(MA), _ptr(flags), stream), "gcdm_geom_finish")
+        M, A = (int(v) for v in MA.cpu())
+        sizes = (ptr_all[1:M + 1] - ptr_all[:M]).cpu().numpy()          # the host mirror of the sizes: with (M, A) the read-back of the ingestion
+        del staging, chunk, ws
+        orders = geom_split_orders(sizes, permutation, val_proportion, test_proportion, filter_size)
+        out = {}
+        for name in GEOM_SPLITS:
+            order, split_indices = orders[name]
+            n = torch.from_numpy(sizes[order])
+            ptr_out = torch.zeros(len(order) + 1, dtype=torch.int64)
+            ptr_out[1:] = torch.cumsum(n, 0)
+            A_out = int(ptr_out[-1])
+            z, pos = torch.empty(A_out, dtype=torch.int32, device=dev), torch.empty((A_out, 3), dtype=torch.float32, device=dev)
+            order_dev, ptr_dev = torch.from_numpy(order).to(dev), ptr_out.to(dev)
+            _chk(lib.gcdm_geom_gather(_ptr(ptr_all), _ptr(z_all), _ptr(pos_all), M, A, _ptr(order_dev), _ptr(ptr_dev), len(order), A_out, _ptr(z),
+                                      _ptr(pos), _ptr(flags), stream), "gcdm_geom_gather")
+            self = cls.__new__(cls)
+            self.stats = {}
+            self._init_ragged(n, z, pos, {}, torch.arange(len(order), dtype=torch.int64), included_species, dev, -1, (),
+                              max_atoms=int(n.max()) if len(order) else 0)
+            self.sorted_by_size, self.split_indices = True, split_indices
+            out[name] = self
+        f = int(flags.item())                      # also waits for the gathers before the raw buffers go
+        del z_all, pos_all, ptr_all
+        if f & _native.GEOM_FLAG_BAD_ROW:
+            raise ValueError("the conformer file holds a row with an atomic number < 1 or a value that is not finite")
+        if f:
+            raise RuntimeError(f"the GEOM ingestion raised device flags {f}: the sizes on the device did not add up")
+        return out
+
+    @classmethod
+    def from_geom_file(cls, file_or_array, device, split: str = "train", **kw) -> "MoleculeDataset":
+        """One split of ``geom_splits`` (same arguments)."""
+        if split not in GEOM_SPLITS:
+            raise ValueError(f"split must be one of {GEOM_SPLITS}, got {split!r}")
+        return cls.geom_splits(file_or_array, device, **kw)[split]
+
     def __len__(self) -> int:
         return self.num_pts
 
@@ -199,8 +339,8 @@ class MoleculeDataset:
         return {t: int((zs == int(s)).sum()) for t, s in enumerate(self.included_species)}
 
     def loader(self, batch_size: int, shuffle: bool = True, drop_last: bool = False, seed: int = 0, layout: str = "padded", rank: int = 0,
-               world: int = 1) -> "DeviceLoader":
-        return DeviceLoader(self, batch_size, shuffle, drop_last, seed, layout, rank, world)
+               world: int = 1, sequential: bool = False) -> "DeviceLoader":
+        return DeviceLoader(self, batch_size, shuffle, drop_last, seed, layout, rank, world, sequential)
 
     def collate(self, perm: torch.Tensor, first: int, B: int, pad_to: int, sizes: np.ndarray) -> AttrDict:
         """One batch of molecules ``perm[first : first + B]`` (``perm`` int64 on the device, ``sizes`` their atom counts from the host mirror):
@@ -242,10 +382,12 @@ class MoleculeDataset:
 class DeviceLoader:
     """Iterates a MoleculeDataset in batches; ``set_epoch(e)`` as on a DistributedSampler.  The index stream is
     ``distributed_indices(len(dataset), shuffle, seed, epoch, rank, world)``, uploaded once per epoch; ``drop_last`` drops a short last batch.
-    ``layout="padded"``: every molecule takes ``dataset.max_atoms`` rows (the reference's batches); ``"compact"``: present atoms only."""
+    ``layout="padded"``: every molecule takes ``dataset.max_atoms`` rows (the reference's batches); ``"compact"``: present atoms only.
+    ``sequential=True`` (GEOM's ``dataloader_cfg.sequential``): the batches of ``sequential_batches`` over a size-sorted data set, every batch of
+    one molecule size, so both layouts hold present atoms only and ``all_present`` is true; it needs ``shuffle=False`` and ``world == 1``."""
 
     def __init__(self, dataset: MoleculeDataset, batch_size: int, shuffle: bool = True, drop_last: bool = False, seed: int = 0, layout: str = "padded",
-                 rank: int = 0, world: int = 1):
+                 rank: int = 0, world: int = 1, sequential: bool = False):
         if layout not in ("padded", "compact"):
             raise ValueError(f"layout must be 'padded' or 'compact', got {layout!r}")
         if int(batch_size) < 1:
@@ -254,12 +396,23 @@ class DeviceLoader:
         self.seed, self.layout, self.rank, self.world = int(seed), layout, int(rank), int(world)
         self.pad_to = dataset.max_atoms if layout == "padded" else 0
         self.epoch, self._perm_epoch = 0, None
+        self.sequential = bool(sequential)
+        if self.sequential:
+            if self.shuffle:
+                raise ValueError("sequential batches need shuffle=False: they walk the size-sorted data set in order")
+            if self.world != 1:
+                raise ValueError(f"sequential batches need world == 1, got world = {self.world}: they are not built under data-parallel ranks")
+            if not getattr(dataset, "sorted_by_size", False):
+                raise ValueError("sequential batches need a size-sorted data set (MoleculeDataset.geom_splits / from_geom_file): this one is not")
+            self._firsts, self._counts = sequential_batches(len(dataset), self.batch_size, self.drop_last, dataset.split_indices)
         self.indices = distributed_indices(len(dataset), self.shuffle, self.seed, 0, self.rank, self.world)
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
 
     def __len__(self) -> int:
+        if self.sequential:
+            return len(self._counts)
         n = len(self.indices)
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
 
@@ -276,6 +429,14 @@ class DeviceLoader:
         return self
 
     def __next__(self) -> AttrDict:
+        if self.sequential:
+            k = self._cursor
+            if k >= len(self._counts):
+                raise StopIteration
+            self._cursor = k + 1
+            first, B = int(self._firsts[k]), int(self._counts[k])
+            sizes = self._sizes[first:first + B]
+            return self.dataset.collate(self._perm, first, B, int(sizes[0]) if self.layout == "padded" else 0, sizes)
         first, n = self._cursor, len(self.indices)
         B = min(self.batch_size, n - first)
         if B <= 0 or (self.drop_last and B < self.batch_size):
