@@ -27,6 +27,8 @@ from .data import MoleculeDataset, DeviceLoader, PropertiesDistribution         
 from .sdf import write_sdf_file, build_molecules, bond_order_matrices, Molecule  # noqa: F401
 from .xyz import save_xyz_file, write_xyz_file                                  # noqa: F401
 from .stability import check_molecular_stability, check_molecular_stability_batch, get_bond_length_arrays, CategoricalDistribution  # noqa: F401
+from . import metrics                                                            # noqa: F401
+from .metrics import GraphMolecularMetrics, molecule_graph_keys                  # noqa: F401
 
 __all__ = [
     "AttrDict", "default_cfgs", "load_cfg_tree", "dataset_info", "GCP", "GCP2", "GCPEmbedding", "GCPMessagePassing", "GCPInteractions", "GCPLayerNorm",
@@ -37,4 +39,5 @@ __all__ = [
     "save_xyz_file", "write_xyz_file", "write_sdf_file", "build_molecules", "bond_order_matrices", "Molecule", "F16RangeError",
     "optim", "TrainingUpdate", "BucketedUpdate", "classifier", "EGNN", "get_classifier", "property_mae",
     "data", "MoleculeDataset", "DeviceLoader", "PropertiesDistribution",
+    "metrics", "GraphMolecularMetrics", "molecule_graph_keys",
 ]

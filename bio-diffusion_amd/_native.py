@@ -28,7 +28,8 @@ OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(
                os.path.join(_HERE, "csrc", "gcdm_ops.bucket.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_grad_bucket.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.data.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_data.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.geom.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_geom.h"),
-               os.path.join(os.path.dirname(_HERE), "include", "gcdm_matrix_mode.h")]
+               os.path.join(_HERE, "csrc", "gcdm_ops.molgraph.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_molgraph.h"),
+               os.path.join(os.path.dirname(_HERE), "include", "gcdm_hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_matrix_mode.h")]
 ABI_VERSION = 2
 
 FLAG_NAN_VEL, FLAG_MEAN_NOT_ZERO, FLAG_COG_DRIFT, FLAG_F16_RANGE = 1, 2, 4, 8
@@ -244,6 +245,21 @@ GEOM_RESTYPES = {"gcdm_geom_workspace_bytes": C.c_int64}
 GEOM_TILE, GEOM_STATE_WORDS, GEOM_MAX_ROWS = 1024, 4, 2147483647                              # GCDM_GEOM_*
 GEOM_FLAG_BAD_ROW, GEOM_FLAG_CAPACITY, GEOM_FLAG_ACCOUNT = 1, 2, 4                            # GCDM_GEOM_FLAG_*
 GEOM_WS_BYTES, GEOM_WS_LAUNCHES, GEOM_WS_TILE = 0, 1, 2                                       # GCDM_GEOM_WS_*
+
+
+# validity, fragments and permutation-invariant graph keys of molecules (include/gcdm_molgraph.h), exported from the same library
+class GcdmMolGraphTables(C.Structure):
+    _fields_ = [("bonds", GcdmBondTables), ("atomic_number", C.c_int32 * STABILITY_MAX_TYPES), ("valence_cap", C.c_int32 * STABILITY_MAX_TYPES),
+                ("types_are_atomic_numbers", C.c_int32)]
+
+
+MOLGRAPH_SIGNATURES = {
+    "gcdm_molgraph_keys": [C.POINTER(GcdmMolGraphTables), P, I64, P, P, I64, P, P, P],
+    "gcdm_molgraph_keys_from_orders": [C.POINTER(GcdmMolGraphTables), P, P, I64, P, P, P, P, P],
+}
+MOLGRAPH_RESTYPES = {}
+MOLGRAPH_MAX_ATOMS, MOLGRAPH_ROUNDS = 192, 16                                                 # GCDM_MOLGRAPH_*
+MOLGRAPH_K = (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0xD6E8FEB86659FD93, 0xA0761D6478BD642F)      # GCDM_MOLGRAPH_K1..K5
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -259,7 +275,8 @@ def load_ops() -> C.CDLL:
         fn = getattr(lib, name)
         fn.argtypes = sig
         fn.restype = {**MP_TRAIN_RESTYPES, **MP_TILE_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
-    for table, restypes in ((MATRIX_MODE_SIGNATURES, MATRIX_MODE_RESTYPES), (DATA_SIGNATURES, DATA_RESTYPES), (GEOM_SIGNATURES, GEOM_RESTYPES)):
+    for table, restypes in ((MATRIX_MODE_SIGNATURES, MATRIX_MODE_RESTYPES), (DATA_SIGNATURES, DATA_RESTYPES), (GEOM_SIGNATURES, GEOM_RESTYPES),
+                            (MOLGRAPH_SIGNATURES, MOLGRAPH_RESTYPES)):
         for name, sig in table.items():
             fn = getattr(lib, name)
             fn.argtypes = sig

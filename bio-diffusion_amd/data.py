@@ -338,6 +338,20 @@ class MoleculeDataset:
         zs = self._z_host.to(torch.int64)
         return {t: int((zs == int(s)).sum()) for t, s in enumerate(self.included_species)}
 
+    @torch.inference_mode()
+    def graph_keys(self, dataset_info: Dict[str, Any], valence_caps: Optional[Dict[str, int]] = None) -> torch.Tensor:
+        """The sorted distinct graph keys (metrics.molecule_graph_keys) of the split's molecules that are valid AND in one fragment: what
+        novelty is taken against.  compute_qm9_smiles (rdkit_functions.py:32-76) keeps the whole-molecule SMILES of the sanitisable molecules,
+        and a dotted SMILES can never equal a largest-fragment one.  One launch over ``pos`` / ``z`` / ``atom_ptr``, the atomic numbers mapped
+        through the vocabulary of ``dataset_info`` on the device."""
+        from . import metrics
+        if self.device.type != "cuda":
+            raise RuntimeError("MoleculeDataset.graph_keys runs on the GPU only (no CPU fallback)")
+        tb = metrics.graph_tables(dataset_info, valence_caps, types_are_atomic_numbers=True)
+        keys, info = metrics._launch(tb, self.pos, self.z, self.atom_ptr, self.M)
+        keep = (info[:, 0] == 1) & (info[:, 1] == 1)
+        return torch.unique(keys[keep])
+
     def loader(self, batch_size: int, shuffle: bool = True, drop_last: bool = False, seed: int = 0, layout: str = "padded", rank: int = 0,
                world: int = 1, sequential: bool = False) -> "DeviceLoader":
         return DeviceLoader(self, batch_size, shuffle, drop_last, seed, layout, rank, world, sequential)

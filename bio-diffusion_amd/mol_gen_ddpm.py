@@ -23,6 +23,7 @@ from torch import nn
 from .config import cfg_get, dataset_info as _dataset_info
 from .gcpnet import GCPNetDynamics
 from .stability import CategoricalDistribution, check_molecular_stability_batch
+from .metrics import GraphMolecularMetrics, molecule_graph_keys
 from .xyz import save_xyz_file
 from .variational_diffusion import EquivariantVariationalDiffusion, _segment_mean_sub
 
@@ -173,7 +174,7 @@ class _MoleculeGenerationDDPM(nn.Module):
         self.props_distr = None   # PropertiesDistribution needs training data: attach_dataset(data.MoleculeDataset) sets it
         # qm9_mol_gen_ddpm.py:196-199: node-type statistics of the training set, for the KL reported by analyze_samples
         self.node_type_distribution = CategoricalDistribution(self.dataset_info["atom_types"], self.dataset_info["atom_encoder"])
-        self.molecular_metrics = None   # BasicMolecularMetrics needs RDKit + the training SMILES (out of scope); attach one to get validity etc.
+        self.molecular_metrics = None   # attach_molecular_metrics() sets it (metrics.GraphMolecularMetrics: validity etc. without RDKit)
         self._init_kwargs = dict(model_cfg=model_cfg, module_cfg=module_cfg, layer_cfg=layer_cfg, diffusion_cfg=diffusion_cfg,
                                  dataloader_cfg=dataloader_cfg, path_cfg=path_cfg)
 
@@ -191,6 +192,19 @@ class _MoleculeGenerationDDPM(nn.Module):
             raise ValueError("attach_dataset: no properties to condition on (the data set was built without `conditioning`)")
         self.props_distr = PropertiesDistribution(dataset, props, num_bins=num_bins, normalizer=dataset.mean_mad(props))
         return self.props_distr
+
+    def attach_molecular_metrics(self, dataset: Any = None, dataset_keys: Optional[torch.Tensor] = None,
+                                 valence_caps: Optional[Dict[str, int]] = None):
+        """Sets ``molecular_metrics`` to a metrics.GraphMolecularMetrics, the stand-in for the reference's BasicMolecularMetrics
+        (qm9_mol_gen_ddpm.py:201-206): from then on ``sample_and_analyze`` fills ``validity``, ``uniqueness`` and ``novelty``.  Novelty is
+        taken against ``dataset_keys`` or, with a ``dataset`` (data.MoleculeDataset, the training split), against its ``graph_keys``; with
+        neither it is 0.0, as in the reference without a SMILES list.  Returns the metrics object."""
+        if dataset is not None and dataset_keys is not None:
+            raise ValueError("attach_molecular_metrics takes a dataset or its keys, not both")
+        if dataset is not None:
+            dataset_keys = dataset.graph_keys(self.dataset_info, valence_caps=valence_caps)
+        self.molecular_metrics = GraphMolecularMetrics(self.dataset_info, dataset_keys=dataset_keys, valence_caps=valence_caps)
+        return self.molecular_metrics
 
     # the reference calls ``model.load_from_checkpoint(...)`` on an instance (mol_gen_sample.py:113-122)
     def load_from_checkpoint(self, checkpoint_path: str, map_location: Any = None, strict: bool = True, **kwargs):
@@ -546,7 +560,8 @@ class _MoleculeGenerationDDPM(nn.Module):
         separate handles / streams (`mol_gen_sample_concurrent`): same samples, better use of the chip at the reference's batch
         size of 100.  `packed_batches = K` instead lays K batches end to end in one packed plan on the primary handle
         (`mol_gen_sample_packed`): the same samples again, without the lane handles; it excludes `concurrent_batches > 1`.
-        `save_molecules` (xyz files) is `sample_and_save`."""
+        `save_molecules` (xyz files) is `sample_and_save`.  With `attach_molecular_metrics` each batch also gets one launch of
+        `molecule_graph_keys` next to the stability launch, in every mode, and the three RDKit-free metrics are filled in."""
         if packed_batches is not None:
             if int(concurrent_batches) > 1:
                 raise ValueError("packed_batches and concurrent_batches > 1 exclude each other: batches are either packed into one plan or run on lane handles")
@@ -556,6 +571,9 @@ class _MoleculeGenerationDDPM(nn.Module):
         batch_size = int(cfg_get(self._init_kwargs["dataloader_cfg"], "batch_size", 64)) if batch_size is None else batch_size
         batch_size = min(batch_size, num_samples)
         results, type_counts = [], torch.zeros(self.num_atom_types, dtype=torch.int64)
+        metrics = self.molecular_metrics
+        if metrics is not None:
+            metrics.reset()
         plan, done = [], 0
         while done < num_samples:                               # draw all sizes first: the same random stream as the sequential driver
             nb = min(batch_size, num_samples - done)
@@ -573,6 +591,8 @@ class _MoleculeGenerationDDPM(nn.Module):
             oh = xh[:, self.num_x_dims:-1] if self.include_charges else xh[:, self.num_x_dims:]
             atom_types = oh.argmax(-1)
             results.append(check_molecular_stability_batch(xh, atom_types, num_nodes, self.dataset_info))
+            if metrics is not None:
+                metrics.update(*molecule_graph_keys(xh, atom_types, num_nodes, self.dataset_info, metrics.valence_caps))
             type_counts.add_(torch.bincount(atom_types, minlength=self.num_atom_types).cpu())
 
         K = max(1, int(concurrent_batches)) if packed_batches is None else int(packed_batches)
@@ -593,7 +613,7 @@ class _MoleculeGenerationDDPM(nn.Module):
                                                            contexts=[c[2] for c in chunk], seeds=[1234 + i0 + j for j in range(len(chunk))])
                 for (xh, _, _), c in zip(outs, chunk):
                     account(xh, c[1])
-        return self.analyze_samples(torch.cat(results).cpu(), type_counts)
+        return self.analyze_samples(torch.cat(results).cpu(), type_counts, metrics)
 
     @torch.inference_mode()
     def evaluate_conditional(self, classifier: Any, property: str, mean: float, mad: float, iterations: int, batch_size: int,
@@ -772,8 +792,9 @@ class _MoleculeGenerationDDPM(nn.Module):
             records.append(record(it, x, one_hot))
         return records
 
-    def analyze_samples(self, stability: torch.Tensor, atom_type_counts: torch.Tensor) -> Dict[str, Any]:
-        """qm9_mol_gen_ddpm.py:846-885 on the device results: `stability` int [M, 3] rows (stable, nr_stable_atoms, n)."""
+    def analyze_samples(self, stability: torch.Tensor, atom_type_counts: torch.Tensor, molecular_metrics: Any = None) -> Dict[str, Any]:
+        """qm9_mol_gen_ddpm.py:846-885 on the device results: `stability` int [M, 3] rows (stable, nr_stable_atoms, n).  `molecular_metrics`:
+        an updated metrics.GraphMolecularMetrics, whose `compute()` fills validity, uniqueness and novelty (None without one)."""
         st = stability.to(torch.int64)
         q = atom_type_counts.to(torch.float64).numpy()
         p = self.node_type_distribution.p
@@ -783,8 +804,10 @@ class _MoleculeGenerationDDPM(nn.Module):
             "kl_div_atom_types": kl,
             "mol_stable": float(st[:, 0].sum()) / float(len(st)),
             "atm_stable": float(st[:, 1].sum()) / float(st[:, 2].sum()),
-            "validity": None, "uniqueness": None, "novelty": None,    # RDKit metrics (BasicMolecularMetrics) are outside the path
+            "validity": None, "uniqueness": None, "novelty": None,    # filled from attach_molecular_metrics' GraphMolecularMetrics below
         }
+        if molecular_metrics is not None:
+            out["validity"], out["uniqueness"], out["novelty"] = (float(v) for v in molecular_metrics.compute())
         return out
 
 
