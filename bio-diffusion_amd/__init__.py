@@ -21,7 +21,7 @@ from . import _native, stability, xyz, sdf                                      
 from . import optim                                                              # noqa: F401
 from .optim import TrainingUpdate, BucketedUpdate                                # noqa: F401
 from . import classifier                                                         # noqa: F401
-from .classifier import EGNN, get_classifier, property_mae                       # noqa: F401
+from .classifier import EGNN, get_classifier, property_mae, train_epoch, save_classifier  # noqa: F401
 from . import data                                                               # noqa: F401
 from .data import MoleculeDataset, DeviceLoader, PropertiesDistribution          # noqa: F401
 from .sdf import write_sdf_file, build_molecules, bond_order_matrices, Molecule  # noqa: F401
@@ -37,7 +37,7 @@ __all__ = [
     "QM9MoleculeGenerationDDPM", "GEOMMoleculeGenerationDDPM",
     "check_molecular_stability", "check_molecular_stability_batch", "get_bond_length_arrays", "CategoricalDistribution",
     "save_xyz_file", "write_xyz_file", "write_sdf_file", "build_molecules", "bond_order_matrices", "Molecule", "F16RangeError",
-    "optim", "TrainingUpdate", "BucketedUpdate", "classifier", "EGNN", "get_classifier", "property_mae",
+    "optim", "TrainingUpdate", "BucketedUpdate", "classifier", "EGNN", "get_classifier", "property_mae", "train_epoch", "save_classifier",
     "data", "MoleculeDataset", "DeviceLoader", "PropertiesDistribution",
     "metrics", "GraphMolecularMetrics", "molecule_graph_keys",
 ]

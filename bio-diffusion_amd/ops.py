@@ -967,3 +967,99 @@ def diffusion_objective(net_out: torch.Tensor, state: ObjectiveState, net_out_0:
     terms = {k: tb[:, i] for i, k in enumerate(OBJECTIVE_TERMS)}
     terms["error_t"], terms["loss_0_x"] = error_t, loss_0_x
     return terms, nll, loss, {k: mb[i] for i, k in enumerate(OBJECTIVE_MEANS)}
+
+
+# ---- the classifier's column-split first edge layer (include/gcdm_classifier_train.h) ------------------------------------------------------------
+class MoleculeEdges:
+    """The classifier's edge set from the molecule sizes alone: the ordered pairs i != j of each molecule, row-major.  Holds the three device
+    tables gcdm_classifier_train_edge_pre_* read (node_mol [N], node_offsets [B + 1] int32, edge_offsets [B + 1] int64) and, made on first
+    use, the two ``Graph`` views the other operators take: ``graph`` (nodes x edges, with its column order in closed form -- nothing is
+    sorted) and ``pool`` (molecules x nodes, for the per-molecule sum).  ``sizes`` is read on the host: E and N size the buffers."""
+
+    def __init__(self, sizes, device):
+        n = torch.as_tensor(sizes).detach().to("cpu", torch.int64).reshape(-1)
+        _shape(bool((n >= 0).all()), f"MoleculeEdges: molecule sizes must be counts >= 0, got {n.tolist()}")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("bio-diffusion_amd operators run on an MI355X only: MoleculeEdges needs a HIP ('cuda') device; there is no CPU fallback")
+        self.sizes, self.device = [int(v) for v in n], dev
+        self.B, self.N, self.E = int(n.numel()), int(n.sum()), int((n * (n - 1)).clamp(min=0).sum())
+        _shape(self.N < 2 ** 31 - 1, f"MoleculeEdges: {self.N} nodes")
+        noff = torch.zeros(self.B + 1, dtype=torch.int64)
+        noff[1:] = torch.cumsum(n, 0)
+        eoff = torch.zeros(self.B + 1, dtype=torch.int64)
+        eoff[1:] = torch.cumsum((n * (n - 1)).clamp(min=0), 0)
+        self.node_offsets = noff.to(torch.int32).to(dev)
+        self.edge_offsets = eoff.to(dev)
+        self._n = n.to(dev)
+        self.node_mol = torch.repeat_interleave(torch.arange(self.B, device=dev), self._n, output_size=self.N).to(torch.int32)
+        self._graph = self._pool = None
+
+    @property
+    def graph(self) -> Graph:
+        if self._graph is None:
+            dev, N, E = self.device, self.N, self.E
+            mol = self.node_mol.to(torch.int64)
+            n_of, o_of, eo_of = self._n[mol], self.node_offsets.to(torch.int64)[mol], self.edge_offsets[mol]      # per node: its molecule's
+            deg = (n_of - 1).clamp(min=0)
+            rowptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+            rowptr[1:] = torch.cumsum(deg, 0)
+            node = torch.repeat_interleave(torch.arange(N, device=dev), deg, output_size=E)      # the row of edge e; also the column of slot e
+            k = torch.arange(E, device=dev) - rowptr[node]                                      # position among the node's n - 1 partners
+            li = node - o_of[node]
+            other = k + (k >= li).to(torch.int64)                                               # the partner's local index, ascending
+            ei = torch.stack([node, o_of[node] + other]).contiguous()
+            # slot e of the column order is the edge (other, li) of the node's molecule: the block walked with stride n - 1
+            colperm = (eo_of[node] + other * (n_of[node] - 1) + li - (li > other).to(torch.int64)).contiguous()
+            ptr = rowptr.to(torch.int32)
+            self._graph = Graph.from_parts(ei, N, ptr, colperm, ptr.clone())
+        return self._graph
+
+    @property
+    def pool(self) -> Graph:
+        if self._pool is None:
+            mol = self.node_mol.to(torch.int64)
+            ei = torch.stack([mol, mol]).contiguous()
+            self._pool = Graph.from_parts(ei, self.B, self.node_offsets, torch.arange(self.N, device=self.device), self.node_offsets.clone())
+        return self._pool
+
+
+class _ClassifierEdgePre(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, B, x, w_r, edges):
+        N, E = edges.N, edges.E
+        _shape(A.dim() == 2 and A.shape[0] == N and A.shape[1] >= 1 and tuple(B.shape) == tuple(A.shape),
+               f"classifier_edge_pre: A {tuple(A.shape)} and B {tuple(B.shape)} must both be [{N}, H]")
+        H = int(A.shape[1])
+        _shape(H <= _native.CLASSIFIER_TRAIN_MAX_H, f"classifier_edge_pre: H = {H} > {_native.CLASSIFIER_TRAIN_MAX_H}")
+        _shape(tuple(x.shape) == (N, 3), f"classifier_edge_pre: x {tuple(x.shape)} must be [{N}, 3]")
+        _shape(w_r.numel() == H, f"classifier_edge_pre: w_r {tuple(w_r.shape)} must hold {H} entries")
+        As, Bs, xs, ws = _f(A), _f(B), _f(x), _f(w_r).reshape(-1)
+        pre = torch.empty((E, H), dtype=torch.float32, device=As.device)
+        radial = torch.empty(E, dtype=torch.float32, device=As.device)
+        _chk(_lib().gcdm_classifier_train_edge_pre_fwd(_p(As), _p(Bs), _p(xs), _p(ws), _p(edges.node_mol), _p(edges.node_offsets), _p(edges.edge_offsets),
+                                                       _p(pre), _p(radial), N, edges.B, E, H, _st(As)), "gcdm_classifier_train_edge_pre_fwd")
+        ctx.edges, ctx.radial, ctx.H, ctx.w_shape = edges, radial, H, w_r.shape
+        return pre
+
+    @staticmethod
+    def backward(ctx, dpre):
+        edges, H = ctx.edges, ctx.H
+        N, E = edges.N, edges.E
+        g = _f(dpre).reshape(E, H)
+        alloc = torch.zeros if E == 0 else torch.empty          # no edges: the library writes nothing, the sums are zero
+        dA, dB = alloc((N, H), dtype=torch.float32, device=g.device), alloc((N, H), dtype=torch.float32, device=g.device)
+        dw = alloc(H, dtype=torch.float32, device=g.device)
+        nbytes = int(_lib().gcdm_classifier_train_workspace_bytes(E, H))
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=g.device) if nbytes > 0 else None
+        _chk(_lib().gcdm_classifier_train_edge_pre_bwd(_p(g), _p(ctx.radial), _p(edges.node_mol), _p(edges.node_offsets), _p(edges.edge_offsets), _p(dA),
+                                                       _p(dB), _p(dw), _p(ws), N, edges.B, E, H, _st(g)), "gcdm_classifier_train_edge_pre_bwd")
+        need = ctx.needs_input_grad
+        return (dA if need[0] else None), (dB if need[1] else None), None, (dw.reshape(ctx.w_shape) if need[3] else None), None
+
+
+def classifier_edge_pre(A: torch.Tensor, B: torch.Tensor, x: torch.Tensor, w_r: torch.Tensor, edges: MoleculeEdges) -> torch.Tensor:
+    """The classifier's first per-edge layer with its weight split by columns, W = [W_s | W_t | w_r]: with A = linear(h, W_s, b) and
+    B = linear(h, W_t), ``pre[(i, j)] = A[i] + B[j] + |x_i - x_j|^2 w_r`` over the ordered pairs i != j of each molecule [E, H].  The radial
+    is computed in the same kernel.  Gradients to A, B and w_r (fixed summation order, no atomics); none to x: positions are data."""
+    return _ClassifierEdgePre.apply(A, B, x, w_r, edges)
