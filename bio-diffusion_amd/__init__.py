@@ -29,6 +29,8 @@ from .xyz import save_xyz_file, write_xyz_file                                  
 from .stability import check_molecular_stability, check_molecular_stability_batch, get_bond_length_arrays, CategoricalDistribution  # noqa: F401
 from . import metrics                                                            # noqa: F401
 from .metrics import GraphMolecularMetrics, molecule_graph_keys                  # noqa: F401
+from . import postprocess                                                        # noqa: F401
+from .postprocess import ProcessedBatch, process_molecules                       # noqa: F401
 
 __all__ = [
     "AttrDict", "default_cfgs", "load_cfg_tree", "dataset_info", "GCP", "GCP2", "GCPEmbedding", "GCPMessagePassing", "GCPInteractions", "GCPLayerNorm",
@@ -39,5 +41,5 @@ __all__ = [
     "save_xyz_file", "write_xyz_file", "write_sdf_file", "build_molecules", "bond_order_matrices", "Molecule", "F16RangeError",
     "optim", "TrainingUpdate", "BucketedUpdate", "classifier", "EGNN", "get_classifier", "property_mae", "train_epoch", "save_classifier",
     "data", "MoleculeDataset", "DeviceLoader", "PropertiesDistribution",
-    "metrics", "GraphMolecularMetrics", "molecule_graph_keys",
+    "metrics", "GraphMolecularMetrics", "molecule_graph_keys", "postprocess", "ProcessedBatch", "process_molecules",
 ]

@@ -29,6 +29,7 @@ OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(
                os.path.join(_HERE, "csrc", "gcdm_ops.data.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_data.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.geom.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_geom.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.molgraph.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_molgraph.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.molproc.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_molproc.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.classifier_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier_train.h"),
                os.path.join(os.path.dirname(_HERE), "include", "gcdm_hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_matrix_mode.h")]
 ABI_VERSION = 2
@@ -261,6 +262,14 @@ MOLGRAPH_SIGNATURES = {
 MOLGRAPH_RESTYPES = {}
 MOLGRAPH_MAX_ATOMS, MOLGRAPH_ROUNDS = 192, 16                                                 # GCDM_MOLGRAPH_*
 MOLGRAPH_K = (0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0xD6E8FEB86659FD93, 0xA0761D6478BD642F)      # GCDM_MOLGRAPH_K1..K5
+# the sanitize and largest-fragment filters of generated molecules on a flat batch (include/gcdm_molproc.h), exported from the same library
+MOLPROC_SIGNATURES = {
+    "gcdm_molproc_workspace_bytes": [I64],
+    "gcdm_molproc_select": [C.POINTER(GcdmMolGraphTables), P, I64, P, P, I64, P, P, I32, P, P, P, P, P, P, P],
+    "gcdm_molproc_emit": [C.POINTER(GcdmMolGraphTables), P, I64, P, P, P, I64] + [P] * 16,
+}
+MOLPROC_RESTYPES = {"gcdm_molproc_workspace_bytes": C.c_int64}
+MOLPROC_SANITIZE, MOLPROC_LARGEST_FRAG, MOLPROC_SCAN_TILE = 1, 2, 256                         # GCDM_MOLPROC_*
 # the classifier's column-split first edge layer for training, forward and backward (include/gcdm_classifier_train.h), exported from the same library
 CLASSIFIER_TRAIN_SIGNATURES = {
     "gcdm_classifier_train_workspace_bytes": [I64, I32],
@@ -286,7 +295,7 @@ def load_ops() -> C.CDLL:
         fn.argtypes = sig
         fn.restype = {**MP_TRAIN_RESTYPES, **MP_TILE_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
     for table, restypes in ((MATRIX_MODE_SIGNATURES, MATRIX_MODE_RESTYPES), (DATA_SIGNATURES, DATA_RESTYPES), (GEOM_SIGNATURES, GEOM_RESTYPES),
-                            (MOLGRAPH_SIGNATURES, MOLGRAPH_RESTYPES), (CLASSIFIER_TRAIN_SIGNATURES, CLASSIFIER_TRAIN_RESTYPES)):
+                            (MOLGRAPH_SIGNATURES, MOLGRAPH_RESTYPES), (MOLPROC_SIGNATURES, MOLPROC_RESTYPES), (CLASSIFIER_TRAIN_SIGNATURES, CLASSIFIER_TRAIN_RESTYPES)):
         for name, sig in table.items():
             fn = getattr(lib, name)
             fn.argtypes = sig

@@ -14,6 +14,7 @@ import logging
 import os
 import pickle
 import re
+import warnings
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -24,6 +25,7 @@ from .config import cfg_get, dataset_info as _dataset_info
 from .gcpnet import GCPNetDynamics
 from .stability import CategoricalDistribution, check_molecular_stability_batch
 from .metrics import GraphMolecularMetrics, molecule_graph_keys
+from .postprocess import process_molecules
 from .xyz import save_xyz_file
 from .variational_diffusion import EquivariantVariationalDiffusion, _segment_mean_sub
 
@@ -381,9 +383,16 @@ class _MoleculeGenerationDDPM(nn.Module):
                            num_resamplings: int = 1, jump_length: int = 1,
                            molecule_builder: Optional[Callable[[torch.Tensor, torch.Tensor, Dict[str, Any]], Any]] = None,
                            **kw) -> List[Any]:
-        """qm9_mol_gen_ddpm.py:1063-1243 up to (not including) the RDKit post-processing.  ``ddpm_mode="inpainting"`` (:1130-1181): RePaint on an
-        all-zero molecule with the nodes of ``node_mask`` fixed (default: the first node of the batch), then every generated molecule is
-        moved back to the given one's centre of mass."""
+        """qm9_mol_gen_ddpm.py:1063-1243.  ``ddpm_mode="inpainting"`` (:1130-1181): RePaint on an all-zero molecule with the nodes of
+        ``node_mask`` fixed (default: the first node of the batch), then every generated molecule is moved back to the given one's centre of
+        mass.  Of the post-processing (``process_molecule``, rdkit_functions.py:323-379) the two graph filters run, on the device
+        (postprocess.py): ``sanitize`` drops the molecules that fail the valence-cap verdict, ``largest_frag`` keeps the largest fragment's
+        atoms; only surviving molecules are returned (with ``sample_chain`` the filters apply per frame, :1194-1209).  ``add_hydrogens``
+        and ``relax_iter`` (AddHs, UFF: RDKit) are not done and warn."""
+        if add_hydrogens or relax_iter > 0:
+            skipped = [name for name, on in (("add_hydrogens", add_hydrogens), ("relax_iter", relax_iter > 0)) if on]
+            warnings.warn(f"generate_molecules: {' and '.join(skipped)} not applied (AddHs and UFF relaxation need RDKit); the molecules are "
+                          "returned without", UserWarning, stacklevel=2)
         if sample_chain:
             assert num_samples == 1, "Chain sampling is only supported for single-molecule batches."
             if ddpm_mode != "unconditional":
@@ -400,6 +409,12 @@ class _MoleculeGenerationDDPM(nn.Module):
                                                     node_mask=node_mask, context=context if self.condition_on_context else None, **kw)
             frames = frames.reshape(T, -1, frames.shape[-1]).flip(0)
             oh = frames[:, :, self.num_x_dims:-1] if self.include_charges else frames[:, :, self.num_x_dims:]
+            if sanitize or largest_frag:                              # T one-molecule entries: the flags apply per frame
+                done = process_molecules(frames[:, :, : self.num_x_dims].reshape(-1, self.num_x_dims).contiguous(), oh.argmax(-1).reshape(-1),
+                                         torch.full((frames.shape[0],), frames.shape[1], dtype=torch.int64), self.dataset_info,
+                                         sanitize=sanitize, largest_frag=largest_frag)
+                return [molecule_builder(pos, at, self.dataset_info) if molecule_builder is not None else (pos, at, None)
+                        for pos, at, _ in done.tuples()]
             mols = []
             for pos, at in zip(frames[:, :, : self.num_x_dims].cpu(), oh.argmax(-1).cpu()):
                 mols.append(molecule_builder(pos, at, self.dataset_info) if molecule_builder is not None else (pos, at, None))
@@ -438,6 +453,10 @@ class _MoleculeGenerationDDPM(nn.Module):
             raise NotImplementedError(f"ddpm_mode {ddpm_mode!r} is not implemented (reference: 'unconditional' | 'inpainting')")
         atom_types = one_hot.argmax(dim=-1)
         counts = torch.unique_consecutive(batch_index, return_counts=True)[1].tolist()
+        if sanitize or largest_frag:
+            done = process_molecules(x, atom_types, torch.tensor(counts, dtype=torch.int64), self.dataset_info,
+                                     charges=charges if self.include_charges else None, sanitize=sanitize, largest_frag=largest_frag)
+            return [molecule_builder(pos, at, self.dataset_info) if molecule_builder is not None else (pos, at, ch) for pos, at, ch in done.tuples()]
         mols, o = [], 0
         for n in counts:
             pos, at = x[o:o + n].cpu(), atom_types[o:o + n].cpu()
