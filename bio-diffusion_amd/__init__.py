@@ -13,6 +13,8 @@ through the alias module ``bio_diffusion_amd`` at the repository root.
 """
 from .config import AttrDict, default_cfgs, load_cfg_tree, dataset_info          # noqa: F401
 from .gcpnet import GCP2, GCPNetDynamics, F16RangeError                                        # noqa: F401
+from . import egnn_dynamics                                                      # noqa: F401
+from .egnn_dynamics import EGNNDynamics                                          # noqa: F401
 from .gcp_modules import GCP, GCPEmbedding, GCPMessagePassing, GCPInteractions, GCPLayerNorm, GCPDropout, get_GCP_with_custom_cfg  # noqa: F401
 from . import ops                                                                # noqa: F401
 from .variational_diffusion import EquivariantVariationalDiffusion, PredefinedNoiseSchedule, NumNodesDistribution  # noqa: F401
@@ -34,7 +36,7 @@ from .postprocess import ProcessedBatch, process_molecules                      
 
 __all__ = [
     "AttrDict", "default_cfgs", "load_cfg_tree", "dataset_info", "GCP", "GCP2", "GCPEmbedding", "GCPMessagePassing", "GCPInteractions", "GCPLayerNorm",
-    "GCPDropout", "get_GCP_with_custom_cfg", "ops", "GCPNetDynamics",
+    "GCPDropout", "get_GCP_with_custom_cfg", "ops", "GCPNetDynamics", "egnn_dynamics", "EGNNDynamics",
     "EquivariantVariationalDiffusion", "PredefinedNoiseSchedule", "NumNodesDistribution",
     "QM9MoleculeGenerationDDPM", "GEOMMoleculeGenerationDDPM",
     "check_molecular_stability", "check_molecular_stability_batch", "get_bond_length_arrays", "CategoricalDistribution",

@@ -23,6 +23,7 @@ from torch import nn
 
 from .config import cfg_get, dataset_info as _dataset_info
 from .gcpnet import GCPNetDynamics
+from .egnn_dynamics import EGNNDynamics
 from .stability import CategoricalDistribution, check_molecular_stability_batch
 from .metrics import GraphMolecularMetrics, molecule_graph_keys
 from .postprocess import process_molecules
@@ -155,8 +156,9 @@ class _MoleculeGenerationDDPM(nn.Module):
     def __init__(self, optimizer: Any = None, scheduler: Any = None, model_cfg: Any = None, module_cfg: Any = None,
                  layer_cfg: Any = None, diffusion_cfg: Any = None, dataloader_cfg: Any = None, path_cfg: Any = None, **kwargs):
         super().__init__()
-        if cfg_get(diffusion_cfg, "dynamics_network", "gcpnet") != "gcpnet":
-            raise NotImplementedError("only dynamics_network=gcpnet is built (EGNN is the reference's ablation baseline)")
+        network = cfg_get(diffusion_cfg, "dynamics_network", "gcpnet")
+        if network not in ("gcpnet", "egnn"):
+            raise NotImplementedError(f"dynamics_network={network!r}: 'gcpnet' and 'egnn' are built (qm9_mol_gen_ddpm.py:101-131)")
         if cfg_get(diffusion_cfg, "ddpm_mode", "unconditional") not in ("unconditional", "inpainting"):
             raise ValueError("unsupported ddpm_mode")
         self.ddpm_mode = cfg_get(diffusion_cfg, "ddpm_mode", "unconditional")
@@ -169,8 +171,11 @@ class _MoleculeGenerationDDPM(nn.Module):
         if name not in self._DATASETS:
             raise ValueError(f"dataset {name!r} not supported by {type(self).__name__}")
         self.dataset_info = _dataset_info(self._DATASETS[name])
-        dynamics_network = GCPNetDynamics(model_cfg=model_cfg, module_cfg=module_cfg, layer_cfg=layer_cfg,
-                                          diffusion_cfg=diffusion_cfg, dataloader_cfg=dataloader_cfg)
+        if network == "egnn":               # the EDM-style baseline (egnn_dynamics.py): the generic sampling loop, training on its operators path
+            dynamics_network = EGNNDynamics(model_cfg=model_cfg, module_cfg=module_cfg, diffusion_cfg=diffusion_cfg, dataloader_cfg=dataloader_cfg)
+        else:
+            dynamics_network = GCPNetDynamics(model_cfg=model_cfg, module_cfg=module_cfg, layer_cfg=layer_cfg,
+                                              diffusion_cfg=diffusion_cfg, dataloader_cfg=dataloader_cfg)
         self.ddpm = EquivariantVariationalDiffusion(dynamics_network=dynamics_network, diffusion_cfg=diffusion_cfg,
                                                     dataloader_cfg=dataloader_cfg, dataset_info=self.dataset_info)
         self.props_distr = None   # PropertiesDistribution needs training data: attach_dataset(data.MoleculeDataset) sets it
@@ -362,7 +367,8 @@ class _MoleculeGenerationDDPM(nn.Module):
         else:
             context = None
         plain = not any(k in kw for k in ("lanes", "noise_fn", "step_callback", "_init_xh")) and kw.get("return_frames", 1) == 1
-        if plain and not fix_noise and num_samples >= DEFAULT_LANES_MIN_SAMPLES and (node_mask is None or bool(node_mask.all())):
+        if plain and not fix_noise and num_samples >= DEFAULT_LANES_MIN_SAMPLES and (node_mask is None or bool(node_mask.all())) \
+                and not self.ddpm.runs_generic_loop_only():
             # plain batches: two slices of the flat batch on two handles / streams (same samples up to fp summation order).  One slice's node kernels
             # and launch tails run under the other's edge kernels: +4-5 % at 1024 QM9 molecules, +17 % at the evaluation driver's 100, +23 % at 64;
             # GEOM-Drugs +-0 at 64, -5 % at 32 (tools/ab_lanes.sh) -- hence the threshold
@@ -586,6 +592,9 @@ class _MoleculeGenerationDDPM(nn.Module):
                 raise ValueError("packed_batches and concurrent_batches > 1 exclude each other: batches are either packed into one plan or run on lane handles")
             if int(packed_batches) < 1:
                 raise ValueError("packed_batches must be >= 1")
+            self.ddpm.refuse_fused_sampler_only("sample_and_analyze(packed_batches=...)")
+        elif int(concurrent_batches) > 1:
+            self.ddpm.refuse_fused_sampler_only("sample_and_analyze(concurrent_batches=...)")
         max_num_nodes = self.dataset_info.get("max_n_nodes", max_num_nodes)
         batch_size = int(cfg_get(self._init_kwargs["dataloader_cfg"], "batch_size", 64)) if batch_size is None else batch_size
         batch_size = min(batch_size, num_samples)
@@ -661,6 +670,7 @@ class _MoleculeGenerationDDPM(nn.Module):
         ``sample_kw`` and nothing else, and ``packed_batches`` no self-conditioned model: refused before any work."""
         mode, K = _chunked_eval_mode(packed_batches, concurrent_batches)
         if mode != "sequential":
+            self.ddpm.refuse_fused_sampler_only(f"evaluate_conditional({'packed_batches' if mode == 'packed' else 'concurrent_batches'}=...)")
             _refuse_for_chunked_eval(mode, bool(getattr(self.ddpm.dynamics_network, "self_condition", False)), sample_kw)
         if not self.condition_on_context:
             raise Exception("Conditional evaluation requires a conditional model (module_cfg.conditioning).")

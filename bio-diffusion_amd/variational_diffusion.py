@@ -739,6 +739,8 @@ class EquivariantVariationalDiffusion(nn.Module):
         (k = 0 for z_T, then one per step, then one for the final decode: the reference's randn call order,
         SURVEY A.5); without it noise comes from on-device Philox(seed)."""
         self._check_x_only_network(generate_x_only)
+        if lanes > 1:
+            self.refuse_fused_sampler_only("mol_gen_sample(lanes > 1)")
         if self._off_fused_kernels(generate_x_only, node_mask):
             # general loop: position-only diffusion, masked nodes inside the loop, or a configuration the fused sampling kernels are not built for
             if _t_norm is not None:
@@ -773,6 +775,18 @@ class EquivariantVariationalDiffusion(nn.Module):
         if generate_x_only and getattr(self.dynamics_network, "num_atom_types", 0) + int(getattr(self.dynamics_network, "include_charges", False)) > 0:
             raise ValueError("generate_x_only needs a dynamics network built without node features (num_atom_types = 0, include_charges = False); "
                              "the reference fails on the feature width of this one too (gcpnet.py:1093-1110)")
+
+    def runs_generic_loop_only(self) -> bool:
+        """Is the dynamics network one the fused sampling kernels are not written for at all (the EGNN dynamics network), so that every
+        sampling entry point runs the generic loop?"""
+        return getattr(self.dynamics_network, "fused_unsupported", None) == "egnn"
+
+    def refuse_fused_sampler_only(self, what: str) -> None:
+        """``what`` exists on the fused sampler alone (lane handles, packed plans): refused by name for the EGNN dynamics network, before
+        any GPU work."""
+        if self.runs_generic_loop_only():
+            raise NotImplementedError(f"{what}: the EGNN dynamics network (dynamics_network=egnn) samples through the generic loop; lanes, "
+                                      "concurrent batches and packed plans are drivers of GCPNet's fused sampling kernels")
 
     def _off_fused_kernels(self, generate_x_only: bool, node_mask: Optional[torch.Tensor] = None) -> bool:
         """Does this call run the general loop on the module path (position-only diffusion, masked nodes inside the loop, a configuration the
@@ -924,6 +938,7 @@ class EquivariantVariationalDiffusion(nn.Module):
     def _sample_batches(self, packed: bool, num_nodes_list, device, num_timesteps, contexts, seeds):
         """The two samplers above behind their defaults.  The packed one checks what needs no device first: one context and one seed per batch, no
         empty batch, no self-conditioned model."""
+        self.refuse_fused_sampler_only("mol_gen_sample_packed" if packed else "mol_gen_sample_concurrent")
         K = len(num_nodes_list)
         contexts = contexts if contexts is not None else [None] * K
         seeds = seeds if seeds is not None else [1234 + b for b in range(K)]
