@@ -32,6 +32,7 @@ OPS_HEADERS = [os.path.join(_HERE, "csrc", "gcdm_ops.tile.hip.h"), os.path.join(
                os.path.join(_HERE, "csrc", "gcdm_ops.molproc.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_molproc.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.classifier_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_classifier_train.h"),
                os.path.join(_HERE, "csrc", "gcdm_ops.egnn_dynamics.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_egnn_dynamics.h"),
+               os.path.join(_HERE, "csrc", "gcdm_ops.egnn_train.hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_egnn_train.h"),
                os.path.join(os.path.dirname(_HERE), "include", "gcdm_hip.h"), os.path.join(os.path.dirname(_HERE), "include", "gcdm_matrix_mode.h")]
 ABI_VERSION = 2
 
@@ -291,6 +292,16 @@ EGNN_DYN_SIGNATURES = {
 EGNN_DYN_RESTYPES = {"gcdm_egnn_dyn_last_error": C.c_char_p, "gcdm_egnn_dyn_workspace_bytes": C.c_int64, "gcdm_egnn_dyn_launches": C.c_int64}
 EGNN_DYN_MAX_H, EGNN_DYN_MAX_EH, EGNN_DYN_M_DIM, EGNN_DYN_COORS_HIDDEN = 256, 1024, 16, 64          # GCDM_EGNN_DYN_*
 EGNN_DYN_LAYER_TENSORS, EGNN_DYN_LAUNCHES_PER_LAYER = 15, 8
+# the per-edge block of an EGNN dynamics layer for training, forward and backward (include/gcdm_egnn_train.h), exported from the same library
+EGNN_TRAIN_SIGNATURES = {
+    "gcdm_egnn_train_last_error": [],
+    "gcdm_egnn_train_workspace_bytes": [I64, I32, I32, I32],
+    "gcdm_egnn_train_launches": [],
+    "gcdm_egnn_train_edge_fwd": [P] * 17 + [I64, I64, I32, I32, I32, P],
+    "gcdm_egnn_train_edge_bwd": [P] * 29 + [I64, I64, I32, I32, I32, P],
+}
+EGNN_TRAIN_RESTYPES = {"gcdm_egnn_train_last_error": C.c_char_p, "gcdm_egnn_train_workspace_bytes": C.c_int64, "gcdm_egnn_train_launches": C.c_int64}
+EGNN_TRAIN_MAX_GROUPS, EGNN_TRAIN_BWD_LAUNCHES = 256, 2                                             # GCDM_EGNN_TRAIN_*
 _ops_lib: Optional[C.CDLL] = None
 
 
@@ -308,7 +319,7 @@ def load_ops() -> C.CDLL:
         fn.restype = {**MP_TRAIN_RESTYPES, **MP_TILE_RESTYPES, **GCP2_RESTYPES, **OPTIM_RESTYPES, **CLASSIFIER_RESTYPES, **OBJECTIVE_RESTYPES, **GRAD_BUCKET_RESTYPES}.get(name, C.c_int)
     for table, restypes in ((MATRIX_MODE_SIGNATURES, MATRIX_MODE_RESTYPES), (DATA_SIGNATURES, DATA_RESTYPES), (GEOM_SIGNATURES, GEOM_RESTYPES),
                             (MOLGRAPH_SIGNATURES, MOLGRAPH_RESTYPES), (MOLPROC_SIGNATURES, MOLPROC_RESTYPES), (CLASSIFIER_TRAIN_SIGNATURES, CLASSIFIER_TRAIN_RESTYPES),
-                            (EGNN_DYN_SIGNATURES, EGNN_DYN_RESTYPES)):
+                            (EGNN_DYN_SIGNATURES, EGNN_DYN_RESTYPES), (EGNN_TRAIN_SIGNATURES, EGNN_TRAIN_RESTYPES)):
         for name, sig in table.items():
             fn = getattr(lib, name)
             fn.argtypes = sig

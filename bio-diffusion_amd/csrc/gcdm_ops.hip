@@ -36,3 +36,5 @@
 #include "gcdm_ops.classifier_train.hip.h"
 #include "../../include/gcdm_egnn_dynamics.h"
 #include "gcdm_ops.egnn_dynamics.hip.h"
+#include "../../include/gcdm_egnn_train.h"
+#include "gcdm_ops.egnn_train.hip.h"

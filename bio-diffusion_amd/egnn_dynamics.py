@@ -11,6 +11,13 @@ Two paths (``set_path``), switched like the classifier's:
   nothing of size [E, .], one node kernel for the graph-mode LayerNorm.  Forward only: when a gradient is being recorded or the mask has a
   False entry the call runs ``"operators"`` instead, silently.
 
+Training (a forward that records a gradient) has two paths of its own (``set_train_path``): ``"operators"`` (the default) as above, and
+``"fused"``: with every node present, everything of a layer that is per edge -- edge_mlp, coors_mlp, the coordinate term and the two receiver
+sums -- is one differentiable operator, ``ops.egnn_edge_block`` (include/gcdm_egnn_train.h), fed by the column split of edge_mlp.0 written in
+operators so that the gradients reach edge_mlp.0 and edge_embedding through the fold; LayerNorm, node_mlp and the residual stay on the operators.
+Its gradient of the coordinates never forms the diagonal edges' cancelling pair, so it differs from the ``"operators"`` gradient by more than
+rounding in x-dependent terms and is the closer one to the true gradient.
+
 Dropout (the reference constructs the layers with dropout = 0), Fourier features, soft edges, global attention and ``recalc`` are not built.
 There is no CPU / eager path: CPU tensors raise.  The module itself constructs on the CPU (state dicts, checkpoints)."""
 from __future__ import annotations
@@ -26,6 +33,7 @@ from . import _native, ops
 from .config import cfg_get
 
 PATHS = ("fused", "operators")
+TRAIN_PATHS = ("operators", "fused")
 M_DIM = _native.EGNN_DYN_M_DIM
 COORS_HIDDEN = _native.EGNN_DYN_COORS_HIDDEN
 NODE_FEATURE_DIFFUSION_TARGETS = ("atom_types_and_coords",)
@@ -162,6 +170,9 @@ class EGNNDynamics(nn.Module):
             self.fused_layers_unsupported = f"e_hidden_dim = {Eh}: the fused layers take up to {_native.EGNN_DYN_MAX_EH}"
         self.launches = 0                       # fused edge-kernel launches of this module so far (one per layer per fused forward)
         self.fused_forwards = 0
+        self._train_path = "operators"
+        self.train_fused_forwards = 0           # forwards that recorded a gradient on the fused training path
+        self.train_edge_blocks = 0              # ops.egnn_edge_block calls of this module so far (one per layer per such forward)
         self._packed: Optional[torch.Tensor] = None
         self._packed_key: Any = None
         self._plan: Optional[_Plan] = None
@@ -179,6 +190,22 @@ class EGNNDynamics(nn.Module):
         if path not in PATHS:
             raise ValueError(f"path must be one of {PATHS}, got {path!r}")
         self._path = path
+        return self
+
+    @property
+    def train_path(self) -> str:
+        return self._train_path
+
+    def set_train_path(self, path: str) -> "EGNNDynamics":
+        """The path of a forward that records a gradient.  "operators" (the default): the autograd operators.  "fused": ops.egnn_edge_block per
+        layer whenever every node is present, the operators otherwise.  ``set_path`` keeps its meaning for forwards without a gradient."""
+        if path not in TRAIN_PATHS:
+            raise ValueError(f"train path must be one of {TRAIN_PATHS}, got {path!r}")
+        if path == "fused":
+            why = ops.egnn_edge_block_why_not(self.node_dims[0], self.edge_dims[0], self.edge_input_dims[0])
+            if why is not None:
+                raise NotImplementedError(f"the fused EGNN training path does not implement this configuration ({why})")
+        self._train_path = path
         return self
 
     @contextlib.contextmanager
@@ -284,6 +311,44 @@ class EGNNDynamics(nn.Module):
             x = x + dx
         return self._finish(x, h, x_init, bi, mask, mf)
 
+    # ---- the fused training path ------------------------------------------------------------------------------------------------------------
+    def forward_train_fused(self, batch: Any, xh: torch.Tensor, t: torch.Tensor, xh_self_cond: Optional[torch.Tensor] = None,
+                            probe: Optional[dict] = None) -> torch.Tensor:
+        """forward_operators with the per-edge part of every layer on ops.egnn_edge_block; every node must be present."""
+        if torch.is_grad_enabled() and xh.requires_grad:
+            raise NotImplementedError("EGNNDynamics (bio-diffusion_amd): gradients with respect to the input xh are not built (parameter gradients "
+                                      "only -- the edge features of the network input have no backward); detach xh")
+        bi, mask = cfg_get(batch, "batch"), cfg_get(batch, "mask")
+        plan = self._plan_of(bi, mask)
+        if not plan.all_present:
+            raise ValueError("the fused EGNN training path serves batches without masked nodes; use the operators path")
+        dev, N = xh.device, xh.shape[0]
+        H, Eh, e_in, _ = self._dims()
+        mf = torch.ones((N, 1), dtype=torch.float32, device=dev)
+        x_init, h, x_sc = self._features(batch, xh, t, xh_self_cond, mf)
+        x = ops.centralize(x_init, bi, None)
+        h = ops.linear(h, self.node_embedding.weight, self.node_embedding.bias)
+        fold = torch.cat((self.edge_embedding.weight.t(), self.edge_embedding.bias[None, :]), dim=0)        # [e_in + 1, Eh]
+        for layer in self.egnn.mpnn_layers:
+            W1, b1 = layer.edge_mlp[0].weight, layer.edge_mlp[0].bias
+            F = ops.linear(W1[:, 2 * H:2 * H + Eh], fold)                     # [2 D, e_in + 1]: u (, u'), W_e b_emb
+            V = torch.stack((F[:, 0], F[:, 1] if e_in == 2 else torch.zeros_like(F[:, 0]), W1[:, 2 * H + Eh]), dim=0)
+            A = ops.linear(h, W1[:, :H], b1 + F[:, e_in])
+            B = ops.linear(h, W1[:, H:2 * H])
+            m_i, dx = ops.egnn_edge_block(A, B, V, layer.edge_mlp[3].weight, layer.edge_mlp[3].bias, layer.coors_mlp[0].weight,
+                                          layer.coors_mlp[0].bias, layer.coors_mlp[3].weight, layer.coors_mlp[3].bias, layer.coors_norm.scale,
+                                          x, x_init, x_sc, plan.node_offsets, plan.node_mol, H, Eh)
+            self.train_edge_blocks += 1
+            ln = layer.node_norm(h, plan.graph_index, plan.B)
+            if probe is not None:
+                for k, v in (("m", m_i), ("dx", dx), ("ln", ln)):
+                    probe.setdefault(k, []).append(v.detach())
+            h = h + ops.linear(ops.act(ops.linear(torch.cat([ln, m_i], dim=-1), layer.node_mlp[0].weight, layer.node_mlp[0].bias), "silu"),
+                               layer.node_mlp[3].weight, layer.node_mlp[3].bias)
+            x = x + dx
+        self.train_fused_forwards += 1
+        return self._finish(x, h, x_init, bi, None, mf)
+
     # ---- the fused path --------------------------------------------------------------------------------------------------------------------
     def _ordered(self) -> List[torch.Tensor]:
         """The tensors in the order gcdm_egnn_dyn_pack takes them."""
@@ -368,6 +433,11 @@ class EGNNDynamics(nn.Module):
             return False
         return self._plan_of(bi, mask).all_present
 
+    def _use_train_fused(self, xh: torch.Tensor, bi: torch.Tensor, mask: Optional[torch.Tensor]) -> bool:
+        if self._train_path != "fused" or not torch.is_grad_enabled() or not any(p.requires_grad for p in self.parameters()):
+            return False
+        return self._plan_of(bi, mask).all_present
+
     def forward(self, batch: Any, xh: torch.Tensor, t: torch.Tensor, **kwargs: Any) -> Tuple[Any, torch.Tensor]:
         sc = kwargs.get("xh_self_cond")
         if sc is not None and not self.self_condition:
@@ -376,4 +446,6 @@ class EGNNDynamics(nn.Module):
             raise RuntimeError("EGNNDynamics (bio-diffusion_amd) runs on an MI355X only: tensors must be on a HIP ('cuda') device; there is no CPU fallback")
         if self._use_fused(xh, cfg_get(batch, "batch"), cfg_get(batch, "mask")):
             return batch, self.forward_fused(batch, xh, t, xh_self_cond=sc)
+        if self._use_train_fused(xh, cfg_get(batch, "batch"), cfg_get(batch, "mask")):
+            return batch, self.forward_train_fused(batch, xh, t, xh_self_cond=sc)
         return batch, self.forward_operators(batch, xh, t, xh_self_cond=sc)

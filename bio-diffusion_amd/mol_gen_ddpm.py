@@ -171,7 +171,7 @@ class _MoleculeGenerationDDPM(nn.Module):
         if name not in self._DATASETS:
             raise ValueError(f"dataset {name!r} not supported by {type(self).__name__}")
         self.dataset_info = _dataset_info(self._DATASETS[name])
-        if network == "egnn":               # the EDM-style baseline (egnn_dynamics.py): the generic sampling loop, training on its operators path
+        if network == "egnn":               # the EDM-style baseline (egnn_dynamics.py): the generic sampling loop, training on its operators path or, after set_train_path("fused"), its fused edge block
             dynamics_network = EGNNDynamics(model_cfg=model_cfg, module_cfg=module_cfg, diffusion_cfg=diffusion_cfg, dataloader_cfg=dataloader_cfg)
         else:
             dynamics_network = GCPNetDynamics(model_cfg=model_cfg, module_cfg=module_cfg, layer_cfg=layer_cfg,

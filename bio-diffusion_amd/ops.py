@@ -1063,3 +1063,85 @@ def classifier_edge_pre(A: torch.Tensor, B: torch.Tensor, x: torch.Tensor, w_r: 
     B = linear(h, W_t), ``pre[(i, j)] = A[i] + B[j] + |x_i - x_j|^2 w_r`` over the ordered pairs i != j of each molecule [E, H].  The radial
     is computed in the same kernel.  Gradients to A, B and w_r (fixed summation order, no atomics); none to x: positions are data."""
     return _ClassifierEdgePre.apply(A, B, x, w_r, edges)
+
+
+# ---- the per-edge block of an EGNN dynamics layer (include/gcdm_egnn_train.h) -----------------------------------------------------------------
+def egnn_edge_block_why_not(H: int, Eh: int, e_in: int) -> Optional[str]:
+    """None when the kernels of include/gcdm_egnn_train.h serve these widths, else the reason."""
+    if H < 32 or H % 32 or H > _native.EGNN_DYN_MAX_H:
+        return f"h_hidden_dim = {H}: the fused edge block takes a multiple of 32 up to {_native.EGNN_DYN_MAX_H}"
+    if Eh < 1 or Eh > _native.EGNN_DYN_MAX_EH:
+        return f"e_hidden_dim = {Eh}: the fused edge block takes 1 .. {_native.EGNN_DYN_MAX_EH}"
+    if e_in not in (1, 2):
+        return f"e_in = {e_in}: the fused edge block takes 1 or 2 edge input scalars"
+    return None
+
+
+def _egnn_err(what: str) -> "_native.NativeError":
+    return _native.NativeError(f"{what} failed: {_lib().gcdm_egnn_train_last_error().decode()}")
+
+
+class _EgnnEdgeBlock(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, A, B, V, W2, b2, C1, c1b, c2, c2b, scale, x, x0, xsc, node_offsets, node_mol, H, Eh):
+        N, K = int(A.shape[0]) if A.dim() == 2 else -1, 2 * (2 * H + Eh + 1)
+        e_in = 1 if xsc is None else 2
+        why = egnn_edge_block_why_not(H, Eh, e_in)
+        _shape(why is None, f"egnn_edge_block: {why}")
+        _shape(tuple(A.shape) == (N, K) and tuple(B.shape) == (N, K), f"egnn_edge_block: A {tuple(A.shape)} and B {tuple(B.shape)} must both be [N, {K}]")
+        _shape(tuple(V.shape) == (3, K) and tuple(W2.shape) == (_native.EGNN_DYN_M_DIM, K) and b2.numel() == _native.EGNN_DYN_M_DIM,
+               f"egnn_edge_block: V {tuple(V.shape)}, W2 {tuple(W2.shape)}, b2 {tuple(b2.shape)} must be [3, {K}], [16, {K}], [16]")
+        CHn, MDn = _native.EGNN_DYN_COORS_HIDDEN, _native.EGNN_DYN_M_DIM
+        _shape(tuple(C1.shape) == (CHn, MDn) and c1b.numel() == CHn and c2.numel() == CHn and c2b.numel() == 1 and scale.numel() == 1,
+               "egnn_edge_block: C1 [64, 16], c1b [64], c2 [64], c2b [1], scale [1]")
+        _shape(tuple(x.shape) == (N, 3) and tuple(x0.shape) == (N, 3) and (xsc is None or tuple(xsc.shape) == (N, 3)),
+               f"egnn_edge_block: x, x0 (and xsc) must be [{N}, 3]")
+        _shape(node_mol.dtype == torch.int32 and node_offsets.dtype == torch.int32 and node_mol.numel() == N and node_offsets.numel() >= 1,
+               "egnn_edge_block: node_offsets int32 [B + 1], node_mol int32 [N]")
+        ts = [_f(t) for t in (A, B, V, W2, b2, C1, c1b, c2, c2b, scale, x, x0)]
+        xs = None if xsc is None else _f(xsc)
+        nB = int(node_offsets.numel()) - 1
+        M = torch.zeros((N, MDn), dtype=torch.float32, device=ts[0].device)
+        dx = torch.zeros((N, 3), dtype=torch.float32, device=ts[0].device)
+        st = _lib().gcdm_egnn_train_edge_fwd(*[_p(t) for t in ts], _p(xs), _p(node_offsets), _p(node_mol), _p(M), _p(dx), N, nB, H, Eh, e_in, _st(ts[0]))
+        if st != 0:
+            raise _egnn_err("gcdm_egnn_train_edge_fwd")
+        ctx.save_for_backward(*ts, *([] if xs is None else [xs]), node_offsets, node_mol)        # its inputs only: nothing per edge is kept
+        ctx.dims, ctx.shapes = (N, nB, H, Eh, e_in, K), [t.shape for t in (A, B, V, W2, b2, C1, c1b, c2, c2b, scale, x)]
+        return M, dx
+
+    @staticmethod
+    def backward(ctx, gM, gdx):
+        N, nB, H, Eh, e_in, K = ctx.dims
+        saved = ctx.saved_tensors
+        ts, xs = saved[:12], (saved[12] if e_in == 2 else None)
+        node_offsets, node_mol = saved[-2], saved[-1]
+        dev = ts[0].device
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        CHn, MDn = _native.EGNN_DYN_COORS_HIDDEN, _native.EGNN_DYN_M_DIM
+        outs = [new(N, K), new(N, K), new(N, 3), new(3, K), new(MDn, K), new(MDn), new(CHn, MDn), new(CHn), new(CHn), new(1), new(1)]
+        nbytes = int(_lib().gcdm_egnn_train_workspace_bytes(N, H, Eh, e_in))
+        if nbytes < 0:
+            raise _egnn_err("gcdm_egnn_train_workspace_bytes")
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        st = _lib().gcdm_egnn_train_edge_bwd(*[_p(t) for t in ts], _p(xs), _p(node_offsets), _p(node_mol), _p(_f(gM)), _p(_f(gdx)), _p(ws),
+                                             *[_p(t) for t in outs], N, nB, H, Eh, e_in, _st(ts[0]))
+        if st != 0:
+            raise _egnn_err("gcdm_egnn_train_edge_bwd")
+        gA, gB, gx, gV, gW2, gb2, gC1, gc1b, gc2, gc2b, gscale = outs
+        order = [gA, gB, gV, gW2, gb2, gC1, gc1b, gc2, gc2b, gscale, gx]
+        need = ctx.needs_input_grad
+        grads = [(g.reshape(s) if need[k] else None) for k, (g, s) in enumerate(zip(order, ctx.shapes))]
+        return (*grads, None, None, None, None, None, None)
+
+
+def egnn_edge_block(A: torch.Tensor, B: torch.Tensor, V: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, C1: torch.Tensor, c1b: torch.Tensor,
+                    c2: torch.Tensor, c2b: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, x0: torch.Tensor, xsc: Optional[torch.Tensor],
+                    node_offsets: torch.Tensor, node_mol: torch.Tensor, H: int, Eh: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Everything of an EGNN dynamics layer that is per edge, as one operator over the fully connected edges of each molecule (the diagonal
+    included), none of which is materialised: with A = linear(h, W_i, b1 + W_e b_emb), B = linear(h, W_j) [N, K], V = (u, u', w_r) [3, K],
+    ``z1 = A_i + B_j + r0 u + r0sc u' + r w_r``, ``m = silu(W2 silu(z1) + b2)``, ``w = tanh(c2 . silu(C1 m + c1b) + c2b)`` ->
+    (sum_j m_ij [N, 16], sum_j w_ij (x_j - x_i) / max(|x_j - x_i|, 1e-8) scale [N, 3]).  Differentiable in A, B, V, W2, b2, C1, c1b, c2, c2b,
+    scale and x (x0 and xsc are data); the backward recomputes every edge, saves only its inputs, uses no float atomics and never forms the
+    diagonal's cancelling pair in the gradient of x (include/gcdm_egnn_train.h).  ``xsc`` is None with one edge input scalar."""
+    return _EgnnEdgeBlock.apply(A, B, V, W2, b2, C1, c1b, c2, c2b, scale, x, x0, xsc, node_offsets, node_mol, int(H), int(Eh))
